@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """DeepVCP registration hot path benchmark (BASELINE.json metric, config C3 / C4).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...        (one rank per GPU, RCCL)
 
 One step = DeepVCP.forward + deepVCP_loss (the two-pass pose solve) over one batch of
@@ -9,14 +9,22 @@ synthetic KITTI-like pairs (B pairs per GPU, N=16384 points, K=64 key points, ca
 r=2.0 / s=0.4 -> C=1331), inputs resident in HBM, eval mode, random-init weights
 (torch.manual_seed(0)).  Pairs are independent, so ranks shard the pairs with no data-path
 collective ("weak" scaling); the per-pair (R, t) are all-gathered over RCCL once at the end of
-the timed region.  Rank 0 prints one JSON line.  At N=1 the CPU oracle (REF-R restated in
-torch CPU ops) is timed on the same pairs with the same weights and FPS starts (median of
---cpu-pairs), and its R, t are compared with the GPU's.
+the timed region.  Rank 0 prints one JSON line.
 
-Roofline fields: ``roofline`` is the dominant entry point's (largest device
-time per step) executed work against the fp32 / HBM peak with its PMC counters; ``fps_roofline``
-is the FPS chain against its measured step floor and the fp32 VALU peak; ``step_roofline`` and
-``stages`` are SURVEY.md 8(d)'s per-stage ceilings on executed work from one batch in flight;
+A plain run sets up, warms up, times ``--steps`` steps, writes the last timed step's outputs if
+``--dump-outputs DIR`` is given (one float32 / float64 ``DIR/<name>.npy`` per array the step's
+caller receives; the same arguments give the same inputs and FPS starts in every run, so two
+builds can be compared array for array) and prints the result line.  Everything else is behind
+``--full``: the single-batch latency (also with the split-select FPS), the per-kernel HIP-event
+passes and the roofline fields below, and, at N=1, the CPU oracle (REF-R restated in torch CPU
+ops) timed on the same pairs with the same weights and FPS starts (median of --cpu-pairs), its
+R, t compared with the GPU's.  These run after the timed region, so ``--full`` changes neither
+the headline figure nor the dumped outputs.
+
+Roofline fields of a ``--full`` run: ``roofline`` is the dominant entry
+point's (largest device time per step) executed work against the fp32 / HBM peak with its PMC
+counters; ``fps_roofline`` is the FPS chain against its measured step floor and the fp32 VALU
+peak; ``step_roofline`` and ``stages`` are SURVEY.md 8(d)'s per-stage ceilings on executed work from one batch in flight;
 ``live_launch_ms`` are per-launch durations over the timed region (batches in flight contend, so
 they exceed the isolated ones).
 """
@@ -86,7 +94,16 @@ def parse():
     p.add_argument("--s", type=float, default=0.4)
     p.add_argument("--inflight", type=int, default=10,
                    help="independent batches in flight (one stream each); 1 = strictly serial steps")
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed region, also measure everything beside the headline figure: the "
+                        "single-batch latency (and its split-select FPS variant), per-kernel HIP-event timing "
+                        "(live and isolated), the stage / FPS / dominant-kernel rooflines with the PMC summary, "
+                        "and the CPU oracle baseline with its parity check.  Off by default.")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="rank 0 writes what the last timed step returned to its caller as DIR/<name>.npy (float32 / "
+                        "float64): keypoints, vcp, loss (eager issue only), R, t, rot_err_deg, trans_err of its "
+                        "pairs.  Inputs, weights and FPS starts depend only on the arguments.")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle baseline")
     p.add_argument("--graphs", choices=["on", "off"], default="off",
                    help="replay each lane's step as a captured HIP graph (dvcp.graphs.CapturedStep) instead of "
                         "issuing it eagerly, one Python + ctypes call per kernel.  Off by default: on this ROCm the "
@@ -95,7 +112,8 @@ def parse():
     p.add_argument("--lane-priority", choices=["default", "high"], default="default",
                    help="stream priority of the in-flight batches' lanes (FPS chain + head)")
     p.add_argument("--hw-queues", type=int, default=24, help="GPU_MAX_HW_QUEUES for this process (<= 32)")
-    p.add_argument("--stage-report", action="store_true", help="print the per-kernel table to stderr")
+    p.add_argument("--stage-report", action="store_true",
+                   help="print the per-kernel table to stderr (needs --full)")
     p.add_argument("--no-kernel-events", action="store_true",
                    help="skip the eager pass that times every launch at the run's concurrency (live_launch_ms); "
                         "the timed region never carries per-launch events")
@@ -120,6 +138,8 @@ def parse():
                    help="also write the full record (per-stage roofline, live launch times) to this file; it "
                         "always goes to stderr as one 'bench-detail' JSON line")
     a = p.parse_args()
+    if a.stage_report and not a.full:
+        p.error("--stage-report reports the per-stage roofline, which only --full measures")
     c5 = a.config == "c5"
     a.batch = a.batch if a.batch is not None else (2 if c5 else 8)
     a.npoints = a.npoints if a.npoints is not None else (65536 if c5 else 16384)
@@ -179,43 +199,43 @@ def main():
         # per pair: R (9), t (3), rotation error (deg), translation error -> (B, 14)
         return torch.cat([Rp.reshape(B, 9), tp.reshape(B, 3), rot.reshape(B, 1), trans.reshape(B, 1)], 1)
 
-    def step_eager(lane=0):
-        """One pass over one batch: DeepVCP.forward + deepVCP_loss, issued on the lane's stream."""
+    def step_eager(lane=0, keep=None):
+        """One pass over one batch: DeepVCP.forward + deepVCP_loss, issued on the lane's stream.
+        ``keep``: a dict that receives what the step's caller gets (--dump-outputs)."""
         b_src, b_tgt, b_R, b_t = batches[lane]
         starts = plan.starts(model, N)   # this rank's columns of the global batch's draw
         with torch.no_grad(), torch.cuda.stream(lanes[lane]):
             kp, vcp = model(b_src, b_tgt, b_R, t_init, starts=starts)
             loss, Rp, tp = dvcp.deepVCP_loss(kp, vcp, b_R, b_t, 0.5)
             rot, trans = dvcp.registration_errors(Rp, tp, b_R, b_t)  # train.py:112-120 harness
+            if keep is not None:
+                keep.update(keypoints=kp, vcp=vcp, loss=loss, R=Rp, t=tp, rot_err_deg=rot, trans_err=trans)
             return rows(Rp, tp, rot, trans)
 
     graphs = None
 
-    def step_graph(lane=0):
+    def step_graph(lane=0, keep=None):
         """The same step replayed from the lane's captured graph (dvcp.graphs.CapturedStep): one
         host call for the whole dependency graph; the rows are copied out on the lane's stream."""
         starts = plan.starts(model, N)
         out = graphs[lane].replay(starts)
+        if keep is not None:   # the graph's static outputs: read before the lane replays again
+            keep.update(zip(("R", "t", "rot_err_deg", "trans_err"), out))
         with torch.cuda.stream(lanes[lane]):
             return rows(*out)
 
-    def step(lane=0):
-        return step_graph(lane) if graphs is not None else step_eager(lane)
+    def step(lane=0, keep=None):
+        return step_graph(lane, keep) if graphs is not None else step_eager(lane, keep)
 
     if args.graphs == "on":
         # one captured graph per lane (after an eager warm-up inside CapturedStep)
         from dvcp.graphs import CapturedStep
         graphs = [CapturedStep(model, *batches[ln], alpha=0.5, stream=lanes[ln], starts=plan.starts(model, N))
                   for ln in range(P)]
-    # warmup, and the single-batch latency (strictly serial steps on one stream)
+    # warmup: --warmup steps on lane 0, then every other lane once (its streams, allocator pools)
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize()
-    t_lat = time.perf_counter()
-    for _ in range(2):
-        step()
-    torch.cuda.synchronize()
-    latency_ms = (time.perf_counter() - t_lat) / 2 * 1e3
     for lane in range(1, P):
         step(lane)
     torch.cuda.synchronize()
@@ -225,7 +245,8 @@ def main():
     _lib.EVENT_LOG = None   # (per-kernel events: a separate eager pass after the timed region)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    outs = [step(i % P) for i in range(args.steps)]
+    last = {} if args.dump_outputs else None   # the last timed step's outputs, by reference
+    outs = [step(i % P, last if i == args.steps - 1 else None) for i in range(args.steps)]
     t_issue = time.perf_counter() - t0  # host time to issue every step (no sync inside)
     cur = torch.cuda.current_stream(dev)
     for ln in lanes:
@@ -236,11 +257,95 @@ def main():
     res = D.gather_results(res, world)      # the one collective: RCCL all_gather of the rows
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
-    log = []
     if world > 1:
         dist.barrier()
     elapsed = D.max_over_ranks(elapsed, dev if args.dist_backend == "nccl" else torch.device("cpu"))
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, last)
+    ms_step = elapsed / args.steps * 1e3
+    res_cpu = res.cpu()
+    if rank == 0 and args.rows_out:
+        # gathered in rank order (each rank: steps x B rows) -> (steps, global batch, 14)
+        by_step = res_cpu.reshape(world, args.steps, B, 14).permute(1, 0, 2, 3).reshape(args.steps, B * world, 14)
+        torch.save({"rows": by_step.contiguous(), "global_batch": B * world, "steps": args.steps, "world": world,
+                    "columns": "R (9), t (3), rotation error deg, translation error"}, args.rows_out)
+    reg_err = {"rot_deg_mean": float(res_cpu[:, 12].mean()), "rot_deg_max": float(res_cpu[:, 12].max()),
+               "trans_mean": float(res_cpu[:, 13].mean()), "trans_max": float(res_cpu[:, 13].max()),
+               "pairs": int(res_cpu.shape[0]),
+               "note": "vs ground truth (train.py:112-120 metric), random-init weights, R_init = R_gt as train.py:105 passes it"}
+    pairs = B * world * args.steps
+    value = pairs / elapsed
+    c5 = args.config == "c5"
+    S = model.FE1.sa1.npoint
+    C = int((2 * r) / s + 1) ** 3
+    out = {
+        "metric": (f"pairs/sec (full DeepVCP forward) at N=65536, K=256 (C5 stress, {args.feat_dtype} features)" if c5 else
+                   "pairs/sec (full DeepVCP forward) at N=16384, K=64; rot/trans error vs ref"),
+        "value": round(value, 3), "unit": "pairs/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": ("C5: synthetic 65536-point pairs, K=256, DeepVCP.forward + deepVCP_loss (eval), "
+                                f"{args.feat_dtype} target feature table (dvcp_dfe_tgt_f16 for f16)" if c5 else
+                                "C3: KITTI-like synthetic pairs, DeepVCP.forward + deepVCP_loss (eval)"),
+                   "pairs_per_gpu": B, "global_batch": B * world, "n_points": N, "K": K, "r": r, "s": s,
+                   "candidates": C, "fe_npoint": S, "parallelism": f"pairs sharded x{world}, all_gather(R,t)",
+                   "inflight_batches": P, "hw_queues": int(os.environ["GPU_MAX_HW_QUEUES"]),
+                   # what the headline runs where it regroups the reference's arithmetic (DESIGN.md section 3)
+                   "dfe": ("literal: fc1, fc2, fc3 chained as written (dvcp_dfe_tgt_literal)" if args.dfe == "literal" else
+                           "collapsed: fc3.fc2.fc1 as one 32x35 map formed in fp64, rounded once (SURVEY App. A.3 "
+                           "Q14 deviation; --dfe literal runs the chain)") if args.feat_dtype == "f32" else
+                          "collapsed, fp16 feature table (dvcp_dfe_tgt_f16)",
+                   "sa_layer1": "per-point split: W1f.f + b1 once per point, W1x.(p - c) per grouped row (exact in "
+                                "real arithmetic; held to the fp32 bars)",
+                   "fps": _fps_parts_label(N, model.FE1.fps_parts),
+                   "issue": ("each lane's step replayed from a captured HIP graph (dvcp.graphs.CapturedStep)"
+                             if args.graphs == "on" else "eager: one Python + ctypes call per kernel")},
+        "host_issue_ms_per_step": round(t_issue / args.steps * 1e3, 3),
+        "registration_error_vs_gt": reg_err,
+    }
+    if args.full:
+        out.update(full_measurements(args, model, step, step_eager, dev, ms_step, elapsed))
+        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+            out["cpu_baseline"], out["parity"] = cpu_baseline(model, src, tgt, R_gt, t_gt, dev, args.cpu_pairs)
+    if rank == 0:
+        if args.stage_report:
+            for k, v in out["stages"].items():
+                print(f"{k:28s} {v}", file=sys.stderr)
+            print(json.dumps(out["step_roofline"]), file=sys.stderr)
+        # the full record to stderr (and --detail-json); stdout gets ONE compact headline line that
+        # a log tail keeps whole (value, and with --full latency, roofline, cpu_baseline, parity)
+        print("bench-detail " + json.dumps(out), file=sys.stderr, flush=True)
+        if args.detail_json:
+            with open(args.detail_json, "w") as fh:
+                json.dump(out, fh, indent=1)
+        print(json.dumps(headline(out)), flush=True)
+    if world > 1:
+        dist.destroy_process_group()
 
+
+def dump_outputs(path, last):
+    """--dump-outputs: the arrays the last timed step handed its caller, one ``<name>.npy`` each
+    (float64 stays, everything else as float32; a few kilobytes at C3 and C5)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, x in last.items():
+        x = x.detach().cpu()
+        x = x if x.dtype in (torch.float32, torch.float64) else x.to(torch.float32)
+        np.save(os.path.join(path, name + ".npy"), x.contiguous().numpy())
+
+
+def full_measurements(args, model, step, step_eager, dev, ms_step, elapsed):
+    """--full: what the benchmark measures beside the headline figure, after the timed region (the
+    fields DESIGN.md section 6 and the module docstring describe), as entries of the record."""
+    from dvcp import _lib
+    P = max(1, args.inflight)
+    # the single-batch latency (strictly serial steps on one stream)
+    t_lat = time.perf_counter()
+    for _ in range(2):
+        step()
+    torch.cuda.synchronize()
+    latency_ms = (time.perf_counter() - t_lat) / 2 * 1e3
+    log = []
     # ---- per-kernel HIP-event timing (events on the stream each kernel is launched on) --------
     # (1) live over the timed region, the batches in flight: per-launch durations under contention
     #     (graph replays carry no per-kernel events: then an eager pass of the same steps after it)
@@ -248,13 +353,11 @@ def main():
     #     half of its host issue time); this eager pass of the same steps at the same concurrency
     #     times every launch.
     if not args.no_kernel_events:
-        graphs_keep, graphs = graphs, None
         _lib.EVENT_LOG = []
         for i in range(args.steps):
-            step(i % P)
+            step_eager(i % P)
         torch.cuda.synchronize()
         log, _lib.EVENT_LOG = _lib.EVENT_LOG, None
-        graphs = graphs_keep
     live = _per_kernel(log)
     # (2) isolated: the same step with one batch in flight (a few steps on lane 0, after the timed
     #     region), for the per-stage roofline; (3) the FPS step floor probe
@@ -278,53 +381,14 @@ def main():
         torch.cuda.synchronize()
         lat_split = {"parts": args.fps_parts_latency, "ms": round((time.perf_counter() - t_ls) / 2 * 1e3, 3)}
         model.FE1.fps_parts = None
-    ms_step = elapsed / args.steps * 1e3
-    S = model.FE1.sa1.npoint
-    C = int((2 * r) / s + 1) ** 3
     stages, step_roof = stage_roofline(iso, args.iso_steps, ms_step)
     pmc = _pmc(args.config)   # profiles/pmc_summary.json (C3) / pmc_summary_c5.json (C5)
     roofline = dominant_roofline(live, iso, stages, pmc)
     fps_roof = fps_roofline(live, iso, floor_us, pmc)
     roofline["by_kernel_time"] = kernel_time_dominant(iso, stages, fps_roof)
-    res_cpu = res.cpu()
-    if rank == 0 and args.rows_out:
-        # gathered in rank order (each rank: steps x B rows) -> (steps, global batch, 14)
-        by_step = res_cpu.reshape(world, args.steps, B, 14).permute(1, 0, 2, 3).reshape(args.steps, B * world, 14)
-        torch.save({"rows": by_step.contiguous(), "global_batch": B * world, "steps": args.steps, "world": world,
-                    "columns": "R (9), t (3), rotation error deg, translation error"}, args.rows_out)
-    reg_err = {"rot_deg_mean": float(res_cpu[:, 12].mean()), "rot_deg_max": float(res_cpu[:, 12].max()),
-               "trans_mean": float(res_cpu[:, 13].mean()), "trans_max": float(res_cpu[:, 13].max()),
-               "pairs": int(res_cpu.shape[0]),
-               "note": "vs ground truth (train.py:112-120 metric), random-init weights, R_init = R_gt as train.py:105 passes it"}
-    pairs = B * world * args.steps
-    value = pairs / elapsed
-    c5 = args.config == "c5"
-    out = {
-        "metric": (f"pairs/sec (full DeepVCP forward) at N=65536, K=256 (C5 stress, {args.feat_dtype} features)" if c5 else
-                   "pairs/sec (full DeepVCP forward) at N=16384, K=64; rot/trans error vs ref"),
-        "value": round(value, 3), "unit": "pairs/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "config": {"workload": ("C5: synthetic 65536-point pairs, K=256, DeepVCP.forward + deepVCP_loss (eval), "
-                                f"{args.feat_dtype} target feature table (dvcp_dfe_tgt_f16 for f16)" if c5 else
-                                "C3: KITTI-like synthetic pairs, DeepVCP.forward + deepVCP_loss (eval)"),
-                   "pairs_per_gpu": B, "global_batch": B * world, "n_points": N, "K": K, "r": r, "s": s,
-                   "candidates": C, "fe_npoint": S, "parallelism": f"pairs sharded x{world}, all_gather(R,t)",
-                   "inflight_batches": P, "hw_queues": int(os.environ["GPU_MAX_HW_QUEUES"]),
-                   # what the headline runs where it regroups the reference's arithmetic (DESIGN.md section 3)
-                   "dfe": ("literal: fc1, fc2, fc3 chained as written (dvcp_dfe_tgt_literal)" if args.dfe == "literal" else
-                           "collapsed: fc3.fc2.fc1 as one 32x35 map formed in fp64, rounded once (SURVEY App. A.3 "
-                           "Q14 deviation; --dfe literal runs the chain)") if args.feat_dtype == "f32" else
-                          "collapsed, fp16 feature table (dvcp_dfe_tgt_f16)",
-                   "sa_layer1": "per-point split: W1f.f + b1 once per point, W1x.(p - c) per grouped row (exact in "
-                                "real arithmetic; held to the fp32 bars)",
-                   "fps": _fps_parts_label(N, model.FE1.fps_parts),
-                   "issue": ("each lane's step replayed from a captured HIP graph (dvcp.graphs.CapturedStep)"
-                             if args.graphs == "on" else "eager: one Python + ctypes call per kernel")},
+    rec = {
         "latency_ms_single_batch": round(latency_ms, 3),
         "latency_ms_single_batch_split_fps": lat_split,
-        "host_issue_ms_per_step": round(t_issue / args.steps * 1e3, 3),
-        "registration_error_vs_gt": reg_err,
         "roofline": roofline,
         "fps_roofline": fps_roof,
         "step_roofline": step_roof,
@@ -332,27 +396,11 @@ def main():
         "live_launch_ms": {k: round(v["ms"] / v["n"], 4) for k, v in sorted(live.items(), key=lambda kv: -kv[1]["ms"])},
     }
     # HBM fraction of the whole step (north_star asks for it; the path is compute/latency bound)
-    out["hbm_fraction_step"] = round(sum(v["bytes"] for v in iso.values()) / args.iso_steps /
+    rec["hbm_fraction_step"] = round(sum(v["bytes"] for v in iso.values()) / args.iso_steps /
                                      (elapsed / args.steps) / (PEAK_HBM_GBS * 1e9), 6)
-    out["hbm_fraction_note"] = ("algorithmic bytes of every stage (one batch in flight) over ms_per_step x 8 TB/s; "
+    rec["hbm_fraction_note"] = ("algorithmic bytes of every stage (one batch in flight) over ms_per_step x 8 TB/s; "
                                 "the path is compute/latency bound, so this is structurally small")
-
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        out["cpu_baseline"], out["parity"] = cpu_baseline(model, src, tgt, R_gt, t_gt, dev, args.cpu_pairs)
-    if rank == 0:
-        if args.stage_report:
-            for k, v in stages.items():
-                print(f"{k:28s} {v}", file=sys.stderr)
-            print(json.dumps(step_roof), file=sys.stderr)
-        # the full record to stderr (and --detail-json); stdout gets ONE compact headline line that
-        # a log tail keeps whole (value, latency, roofline, cpu_baseline, parity, errors)
-        print("bench-detail " + json.dumps(out), file=sys.stderr, flush=True)
-        if args.detail_json:
-            with open(args.detail_json, "w") as fh:
-                json.dump(out, fh, indent=1)
-        print(json.dumps(headline(out)), flush=True)
-    if world > 1:
-        dist.destroy_process_group()
+    return rec
 
 
 HEADLINE_KEYS = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
@@ -370,10 +418,15 @@ def _fps_parts_label(N, forced=None):
 
 
 def headline(out):
-    """The stdout line: the contract's fields plus latency, roofline, cpu_baseline, parity and the
-    registration error, each trimmed of its long notes; the FPS chain and the step roofline as
-    one-number summaries (the full objects are in the stderr 'bench-detail' line)."""
+    """The stdout line: the contract's fields and the registration error, plus, from a --full run,
+    latency, roofline, cpu_baseline and parity, each trimmed of its long notes, and the FPS chain
+    and the step roofline as one-number summaries (the full objects are in the stderr
+    'bench-detail' line)."""
     h = {k: out[k] for k in HEADLINE_KEYS if k in out}
+    if "registration_error_vs_gt" in out:
+        h["registration_error_vs_gt"] = {k: v for k, v in out["registration_error_vs_gt"].items() if k != "note"}
+    if "roofline" not in out:   # a plain run: the headline figure alone
+        return h
     h["roofline"] = {k: v for k, v in out["roofline"].items() if k not in ("note", "pmc", "work_basis")}
     if out["roofline"].get("pmc"):
         h["roofline"]["pmc"] = {k: v for k, v in out["roofline"]["pmc"].items() if k != "note"}
@@ -381,9 +434,7 @@ def headline(out):
         h["cpu_baseline"] = {k: out["cpu_baseline"][k] for k in ("value", "unit", "cores", "kind", "sample", "cpu_model")}
     if "parity" in out:
         h["parity"] = {k: v for k, v in out["parity"].items() if not k.endswith("_note")}
-    if "registration_error_vs_gt" in out:
-        h["registration_error_vs_gt"] = {k: v for k, v in out["registration_error_vs_gt"].items() if k != "note"}
-    fr = out.get("fps_roofline") or {}
+    fr =out.get("fps_roofline") or {}
     h["fps"] = {k: fr.get(k) for k in ("us_per_centre", "step_floor_us", "frac_of_step_floor", "avg_launch_ms_isolated")}
     h["step_roofline_frac"] = out["step_roofline"]["achieved_frac"]
     h["hbm_fraction_step"] = out["hbm_fraction_step"]

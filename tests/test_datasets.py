@@ -46,16 +46,18 @@ def test_kitti_reading_and_downsample_match_reference(tmp_path):
     np.random.seed(11)
     ds = D.KITTIDataset(root, N=512, device="cpu")
     np.random.seed(11)
-    want = []
+    want, sizes = [], []
     for seq in ("00", "01", "02", "03"):
         path = f"{root}sequences/{seq}/velodyne/"
-        for f in os.listdir(path)[:50]:
+        for f in os.listdir(path)[:50]:   # the reference's order: whatever the file system lists
             want.append(OD.kitti_load(path + f, 512))
+            sizes.append(os.path.getsize(path + f) // 16)   # float32 x, y, z, reflectance rows
     assert len(ds) == len(want) == 12
+    assert sorted(sizes) == sorted([700, 300, 512] * 4)
     for got_p, got_r, (wp, wr) in zip(ds.points, ds.reflectances, want):
         assert torch.equal(got_p, torch.from_numpy(np.ascontiguousarray(wp.T)))
         assert torch.equal(got_r, torch.from_numpy(np.ascontiguousarray(wr.T)))
-    assert all(p.shape[1] == min(512, n) for p, n in zip(ds.points, [700, 300, 512] * 4))
+    assert all(p.shape[1] == min(512, n) for p, n in zip(ds.points, sizes))
 
 
 def test_modelnet_reading(tmp_path):
