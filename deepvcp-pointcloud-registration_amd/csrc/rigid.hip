@@ -7,7 +7,14 @@
 //     contract) of every y_true point against y1 -> keep the int(0.8 n) smallest (ascending,
 //     ties to the lower index) -> R2,t2 = Kabsch(x1, y1[inliers]) (Q12) -> y2 = R2 x1 + t2.
 //   deepVCP_loss (:105-121) needs sum|y2 - y_true1| and sum(y2 - y_true1): written per pair.
+//
+//   Rank-deficient sets (coplanar, collinear, identical points, n = 1 or 2, at most three
+//   non-zero weights): the SVD's null-space vectors are free, so R is not unique there.  kabsch_svd
+//   (rigid_svd.h) completes U to an orthonormal basis with det U = +1: R is then a proper rotation,
+//   finite and orthogonal, optimal on the range of H (tr(R H) = sum sigma); H = 0 gives R = I and
+//   t = cy - cx, as torch.svd does.  The backward kernels skip the pairs with s_i + s_j == 0.
 #include "common.h"
+#include "rigid_svd.h"  // kabsch_svd: the 3x3 Jacobi SVD, R = V U^T, rank-deficient H included
 
 namespace dvcp {
 
@@ -17,61 +24,6 @@ constexpr int kRgMaxN = 1024;
 struct Mat3 {
   double m[3][3];
 };
-
-// One-sided Jacobi SVD of H (3x3): H V = U diag(sig), i.e. H = U diag(sig) V^T.  Returns R = V U^T
-// and U, sig (the backward needs them).
-__device__ void kabsch_svd(const double (&H)[3][3], double (&R)[3][3], double (&U)[3][3], double (&sig)[3]) {
-  double A[3][3], V[3][3];
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) {
-      A[i][j] = H[i][j];
-      V[i][j] = i == j ? 1.0 : 0.0;
-    }
-  for (int sweep = 0; sweep < 40; ++sweep) {
-    bool rotated = false;
-    for (int pq = 0; pq < 3; ++pq) {
-      const int p = pq == 2 ? 1 : 0, q = pq == 0 ? 1 : 2;
-      double alpha = 0, beta = 0, gamma = 0;
-      for (int i = 0; i < 3; ++i) {
-        alpha += A[i][p] * A[i][p];
-        beta += A[i][q] * A[i][q];
-        gamma += A[i][p] * A[i][q];
-      }
-      if (fabs(gamma) <= 1e-300 || fabs(gamma) <= 1e-17 * sqrt(alpha * beta)) continue;
-      rotated = true;
-      const double zeta = (beta - alpha) / (2.0 * gamma);
-      const double t = (zeta >= 0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-      const double c = 1.0 / sqrt(1.0 + t * t), s = c * t;
-      for (int i = 0; i < 3; ++i) {
-        const double ap = A[i][p], aq = A[i][q];
-        A[i][p] = c * ap - s * aq;
-        A[i][q] = s * ap + c * aq;
-        const double vp = V[i][p], vq = V[i][q];
-        V[i][p] = c * vp - s * vq;
-        V[i][q] = s * vp + c * vq;
-      }
-    }
-    if (!rotated) break;
-  }
-  for (int j = 0; j < 3; ++j) sig[j] = sqrt(A[0][j] * A[0][j] + A[1][j] * A[1][j] + A[2][j] * A[2][j]);
-  const double smax = fmax(sig[0], fmax(sig[1], sig[2]));
-  int bad = -1;
-  for (int j = 0; j < 3; ++j) {
-    if (sig[j] > 1e-14 * smax && sig[j] > 0) {
-      for (int i = 0; i < 3; ++i) U[i][j] = A[i][j] / sig[j];
-    } else {
-      bad = j;
-    }
-  }
-  if (bad >= 0) {  // rank-deficient H: complete U with the cross product of the other columns
-    const int a = (bad + 1) % 3, b = (bad + 2) % 3;
-    U[0][bad] = U[1][a] * U[2][b] - U[2][a] * U[1][b];
-    U[1][bad] = U[2][a] * U[0][b] - U[0][a] * U[2][b];
-    U[2][bad] = U[0][a] * U[1][b] - U[1][a] * U[0][b];
-  }
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) R[i][j] = V[i][0] * U[j][0] + V[i][1] * U[j][1] + V[i][2] * U[j][2];
-}
 
 __device__ void kabsch_rotation(const double (&H)[3][3], double (&R)[3][3]) {
   double U[3][3], sig[3];
@@ -734,6 +686,8 @@ extern "C" int dvcp_registration_error(const double* R_pred, const double* t_pre
 }
 
 extern "C" int dvcp_rigid_transform(const double* x, const double* y, int B, int n, double* R, double* t, void* stream) {
+  // n = 1 is accepted: H = 0 has a defined answer (R = I, t = y - x), the reference's own for a
+  // single pair, and the split-FPS guard's fallback can hand the solve one repeated point.
   DVCP_REQUIRE(n > 0 && B >= 0, "dvcp_rigid_transform: n=%d B=%d", n, B);
   if (B == 0) return DVCP_OK;  // empty tensors may carry null pointers
   DVCP_REQUIRE(x && y && R && t, "dvcp_rigid_transform: null pointer");

@@ -423,14 +423,20 @@ int dvcp_fe_head_backward(const float* x, int P, const float* params, const floa
  * solve (ties: the lower index) are solved again (n <= 1024).  x, y: B x 3 x n fp64 ->
  * R (B x 3 x 3), t (B x 3 x 1).  partial (optional, B x 2 fp64, needs R_true (B x 3 x 3) and
  * t_true (B x 3 x 1)): per pair sum |R_true x + t_true - y| and sum |R_true x + t_true - (R x + t)|
- * (the paper's two L1 terms, on every key point). */
+ * (the paper's two L1 terms, on every key point).
+ * Rank-deficient weighted sets (at most three non-zero weights, coplanar or collinear points):
+ * R is a proper rotation, finite and orthogonal, optimal on the range of H and arbitrary off it
+ * (see dvcp_rigid_transform); with or without reflection_fix.  A pair whose weights are all zero
+ * has no centroid (0 / 0): its R and t are NaN, and no other pair is affected. */
 int dvcp_paper_pose(const double* x, const double* y, const double* w, int B, int n, int reflection_fix,
                     double inlier_ratio, const double* R_true, const double* t_true, double* R, double* t,
                     double* partial, void* stream);
 /* Backward of the paper loss alpha * S1 / (3 B n) + (1 - alpha) * S2 / (3 B n) (S1, S2 the sums
  * of dvcp_paper_pose's partial) in y and w: grad_loss (1 fp64, device) -> grad_y (B x 3 x n),
  * grad_w (B x n, optional).  The rejection's selection carries no gradient (piecewise constant);
- * the second solve does (weighted Procrustes derivative, reflection fix included). */
+ * the second solve does (weighted Procrustes derivative, reflection fix included).  Repeated
+ * singular values give a finite gradient; for a rank-deficient H the directions with
+ * s_i + s_j == 0 contribute nothing (the loss is not smooth there) and every gradient is finite. */
 int dvcp_paper_pose_backward(const double* x, const double* y, const double* w, int B, int n,
                              int reflection_fix, double inlier_ratio, const double* R_true,
                              const double* t_true, double alpha, const double* grad_loss, double* grad_y,
@@ -482,7 +488,11 @@ int dvcp_cpg(const float* src, const float* tgt, int64_t t_p, int64_t t_f, int64
              void* stream);
 
 /* Kabsch.  Replaces deepVCP_loss.py:13-44 get_rigid_transform: x, y: B x 3 x n fp64
- * (contiguous) -> R: B x 3 x 3, t: B x 3 x 1 (fp64). R = V U^T, no reflection fix (Q13). */
+ * (contiguous) -> R: B x 3 x 3, t: B x 3 x 1 (fp64). R = V U^T, no reflection fix (Q13).
+ * Any n >= 1.  Rank-deficient H (coplanar or collinear sets, identical points, n <= 3): the SVD's
+ * null-space vectors are free and R is not unique; the returned R is a proper rotation (U is
+ * completed to det +1), finite and orthogonal, with tr(R H) = sum of the singular values, and
+ * t = cy - R cx.  H = 0 (n = 1, identical points) gives R = I, t = cy - cx, as torch.svd does. */
 int dvcp_rigid_transform(const double* x, const double* y, int B, int n, double* R, double* t,
                          void* stream);
 
@@ -490,7 +500,9 @@ int dvcp_rigid_transform(const double* x, const double* y, int B, int n, double*
  * :105-121).  x, y_pred: B x 3 x n fp64; R_true: B x 3 x 3; t_true: B x 3 x 1 (fp64).
  * Outputs: R2 B x 3 x 3, t2 B x 3 x 1, x1 / y_pred2 (optional) B x 3 x n_in with
  * n_in = int(n * 0.8); partial (optional) B x 2: per pair sum|y_pred2 - y_true1| and
- * sum(y_pred2 - y_true1) for the loss. */
+ * sum(y_pred2 - y_true1) for the loss.  n in 2..1024 (n = 1 keeps int(0.8 n) = 0 points and is
+ * rejected, like n > 1024).  n = 2, 3 run the second solve on 1 or 2 points: a rank-deficient H,
+ * solved as dvcp_rigid_transform describes. */
 int dvcp_svd_optimization(const double* x, const double* y_pred, const double* R_true,
                           const double* t_true, int B, int n, double* R2, double* t2,
                           double* x1, double* y2, double* partial, void* stream);
@@ -521,10 +533,12 @@ int dvcp_rigid_apply(int dtype, const void* in, int64_t ib, int64_t ic, int64_t 
 /* deepVCP_loss backward.  Replaces autograd through deepVCP_loss.py:57-121 (torch.svd backward of
  * :29 twice, the gathers of :81-82): dL/dy_pred (B x 3 x n fp64) for
  * loss = alpha*mean|y_true1 - y2| + (1-alpha)*|mean(y2 - y_true1)|.  partial: the forward's
- * (B x 2) per-pair sums; grad_loss: device scalar dL/dloss. */
+ * (B x 2) per-pair sums; grad_loss: device scalar dL/dloss.  n as dvcp_svd_optimization.  Finite for
+ * repeated singular values and for rank-deficient H (pairs with s_i + s_j == 0 contribute 0). */
 /* deepVCP_loss.py:105-121 in full: dvcp_svd_optimization (x1, y2 not returned) plus the scalar
  * loss alpha * mean|y2 - y_true1| + (1 - alpha) * |mean(y2 - y_true1)| (loss: 1 fp64, partial:
- * B x 2 fp64 scratch that also feeds dvcp_svd_optimization_backward). */
+ * B x 2 fp64 scratch that also feeds dvcp_svd_optimization_backward).  n and rank-deficient sets as
+ * dvcp_svd_optimization: n in 2..1024, and R2 is a finite proper rotation where H is rank-deficient. */
 int dvcp_deepvcp_loss(const double* x, const double* y_pred, const double* R_true, const double* t_true,
                       int B, int n, double alpha, double* R2, double* t2, double* partial, double* loss,
                       void* stream);
