@@ -54,7 +54,7 @@ class DeepVCP(nn.Module):
         formed in fp64 and rounded once; the same within 1e-7 on the tests).
         ``fps_parts``: workgroups per cloud of the feature extractor's FPS select rounds (1, 2, 4 or 8;
         None: ops.fps_parts -- one up to 16384 points, eight above, or DVCP_FPS_PARTS).  More workgroups shorten a lone batch's FPS chain (the split
-        select, csrc/fps.hip FpsPartArgs: the same indices); with many batches in flight the CU time
+        select, csrc/fps_select.h FpsPartArgs: the same indices); with many batches in flight the CU time
         they take costs more pairs/s than the shorter chain gains, so one is the default below
         16384 points."""
         super().__init__()

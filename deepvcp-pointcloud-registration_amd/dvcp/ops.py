@@ -25,7 +25,7 @@ FPS_REG_LIMIT = {torch.float32: 16384, torch.float64: 8192}
 
 
 # fp32 clouds the split select takes (several workgroups per cloud, one exchange per round;
-# csrc/fps.hip FpsPartArgs), given a workspace
+# csrc/fps_select.h FpsPartArgs), given a workspace; 2 parts reach 16384 points, 4 reach 32768
 FPS_PART_RANGE = (2048, 65536)
 
 
@@ -43,9 +43,10 @@ def fps_parts(N, dtype=torch.float32):
 
 def fps(xyz, npoint, start, pdim=1, parts=None, err=None):
     """pointnet2_utils.py:63-84.  Returns (idx (B, npoint) int64, centres (B, 3, npoint)).
-    ``parts`` (tests, A/B): workgroups per cloud of the select kernel (1, 2, 4 or 8; fp32 clouds of
-    2048..65536 points), else ``fps_parts``; the indices are the same for every choice.  (Above
-    16384 points, parts=1 takes the per-step split kernel, dvcp_fps_ws's.)  ``err``: the guard's
+    ``parts`` (tests, A/B): workgroups per cloud of the select kernel (1, 2, 4 or 8), else
+    ``fps_parts``; the indices are the same for every choice.  The split select (2, 4, 8) takes fp32
+    clouds from 2048 points up to 16384 at 2 parts, 32768 at 4 and 65536 at 8; beyond that, and
+    with parts=1 above 16384 points, the call takes the per-step split kernel.  ``err``: the guard's
     error word (a zeroed int32 tensor of one element) when the launch takes several workgroups
     per cloud (``fps_uses_guard``); allocated here when None."""
     _lib.require_gpu(xyz, start)

@@ -97,6 +97,30 @@ def test_fps_select_vs_oracle(cuda, case):
     assert torch.equal(got, want), (case, int((got != want).nonzero()[0, 1]) if (got != want).any() else -1)
 
 
+@pytest.mark.parametrize("dt,N", [(torch.float32, n) for n in (2047, 2048, 2049, 4097, 8192, 8193, 10240, 10241, 16384)]
+                         + [(torch.float64, n) for n in (2047, 2048, 2049, 4097, 8192, 8193)],
+                         ids=lambda v: str(v).replace("torch.", ""))
+def test_fps_dispatch_boundaries(cuda, dt, N):
+    """Each edge of the dispatch by cloud size (csrc/fps.hip), default parts, against the oracle, bit
+    for bit, on indices and gathered centres: fps_kernel's last size (2047), then every change of
+    the select kernel's points per lane -- fp32 at 1024 threads 2 | 4 | 8 | 10 | 16 (2048, 2049,
+    4097 and 8192, 8193 and 10240, 10241 and 16384), fp64 at 512 threads 4 | 8 | 16 (2048, 2049 and
+    4097, 8192) -- and the fp64 per-step split kernel above 8192.  A wrong points-per-lane choice
+    drops or duplicates points, which shows within the first rounds: 300 steps."""
+    import oracle as O
+    from dvcp import ops
+    g = torch.Generator().manual_seed(300 + N + (1 if dt == torch.float64 else 0))
+    B, npoint = 2, 300
+    xyz = torch.rand(B, N, 3, generator=g, dtype=dt) * 2 - 1
+    start = torch.randint(0, N, (B,), generator=g)
+    want = O.farthest_point_sample(xyz, npoint, start)
+    got, ctr = ops.fps(xyz.to(cuda), npoint, start.to(cuda), pdim=1)
+    got = got.cpu()
+    assert torch.equal(got, want), (dt, N, int((got != want).nonzero()[0, 1]) if (got != want).any() else -1)
+    gathered = torch.stack([xyz[b, want[b]] for b in range(B)]).transpose(1, 2)
+    assert torch.equal(ctr.cpu(), gathered)
+
+
 def _split_cloud(case, g, B=2):
     N, npoint = 4096, 1500
     if case == "dyadic":

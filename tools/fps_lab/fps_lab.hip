@@ -1,6 +1,8 @@
 // fps_lab.hip -- standalone FPS step-latency laboratory (diagnostics, not part of the product).
 //
-// Compiles the production kernel template (csrc/fps.hip) into one executable together with a
+// Compiles the production kernel templates (csrc/fps_step.hip, csrc/fps_select.h) into one
+// executable -- in the instantiations it lists, most of which the library does not build: other
+// workgroup sizes, points per lane, candidate targets and role placements -- together with a
 // scalar CPU FPS checker, runs configurations of it on a uniform fp32 cloud batch
 // (B x 3 x N, channel-first like the FE input) and prints us/step, mismatches against the CPU
 // result, and -- for the TIMING instantiation -- per-wave step-phase clocks.
@@ -13,7 +15,9 @@
 #include <random>
 #include <vector>
 
-#include "../../deepvcp-pointcloud-registration_amd/csrc/fps.hip"
+// fps_kernel; the select kernels and the split select's workspace layout
+#include "../../deepvcp-pointcloud-registration_amd/csrc/fps_step.hip"
+#include "../../deepvcp-pointcloud-registration_amd/csrc/fps_part.hip"
 
 #define CK(x)                                                                           \
   do {                                                                                  \

@@ -1,4 +1,4 @@
-"""CPU model of fps_select_kernel's round logic (csrc/fps.hip: the floor f, the 256-bin histogram
+"""CPU model of fps_select_kernel's round logic (csrc/fps_select.h: the floor f, the 256-bin histogram
 over (f, vmax], the list capacity, the candidate selection and the prefix acceptance), in fp32 like
 the kernel, to count rounds, scans and rescans per reason under other parameters without a GPU.
 The accepted centres are the exact FPS order (sim(...)["order"]), so a model run is also an FPS.

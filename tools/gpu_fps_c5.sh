@@ -9,7 +9,7 @@ cd "$ROOT" && mkdir -p "$OUT"
 tag=${1:-fc}
 timeout -k 10 240 ./tools/fps_lab/fps_lab 16 16384 10000 > "$OUT/${tag}_fps_lab.log" 2>&1 || exit $?
 timeout -k 10 120 ./tools/fps_lab/fps_lab 16 10000 10000 >> "$OUT/${tag}_fps_lab.log" 2>&1 || exit $?
-# a variant lab binary, when one was built (e.g. -DDVCP_FPS_UPD_PF=1 -o fps_lab_pf)
+# variant lab binaries, when any were built from an edited tree (hipcc ... -o fps_lab_<name>)
 for v in tools/fps_lab/fps_lab_*; do
   [ -x "$v" ] || continue
   echo "== $v" >> "$OUT/${tag}_fps_lab.log"
