@@ -31,6 +31,13 @@
 // the fp32 chain by summation order and the dropped terms, within the fp32 tolerances of the
 // parity tests (tests/test_gpu_kernels.py: rtol = atol = 1e-5; the split's own error against an
 // fp64 evaluation is checked beside the fp32 path's in test_sa_split3_accuracy).
+//
+// Gathers.  A tile's inputs sit behind two dependent loads (list entry, then the U row and the
+// point it names).  The three inference tables (sa1, sa2, sa3) walk each wave's 64-centre batch
+// as one flat tile sequence whose schedule is wave-uniform scalar state, and issue tile t + 2's
+// list entry and tile t + 1's gathers while tile t runs, so no tile waits for its own loads
+// (tests/test_gpu_sa_pipeline.py).  The arithmetic per tile and its order
+// are those of the unpipelined loop, which the plain (not PRE) path still runs.
 #include "common.h"
 #include "morton.h"
 
@@ -77,6 +84,67 @@ __device__ __forceinline__ f32x16 mfma_split3(const Split3& a, const bf16x8& b0,
 }
 
 constexpr int kMfmaWaves = 4;  // centres in flight per workgroup (one per SIMD)
+
+// v of lane j, j wave-uniform (v_readlane)
+template <typename V>
+__device__ __forceinline__ V lane_bcast(V v, int j) {
+  if constexpr (sizeof(V) == 8) {
+    const int64_t u = __builtin_bit_cast(int64_t, v);
+    const int lo = __builtin_amdgcn_readlane(static_cast<int>(u & 0xFFFFFFFF), j);
+    const int hi = __builtin_amdgcn_readlane(static_cast<int>(u >> 32), j);
+    return __builtin_bit_cast(V, (static_cast<int64_t>(hi) << 32) | static_cast<uint32_t>(lo));
+  } else {
+    return __builtin_bit_cast(V, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), j));
+  }
+}
+// v of lane j, j per lane (ds_bpermute; every lane of the wave is active where this is used)
+template <typename V>
+__device__ __forceinline__ V lane_gather(V v, int j) {
+  if constexpr (sizeof(V) == 8) {
+    const int64_t u = __builtin_bit_cast(int64_t, v);
+    const int lo = __builtin_amdgcn_ds_bpermute(j << 2, static_cast<int>(u & 0xFFFFFFFF));
+    const int hi = __builtin_amdgcn_ds_bpermute(j << 2, static_cast<int>(u >> 32));
+    return __builtin_bit_cast(V, (static_cast<int64_t>(hi) << 32) | static_cast<uint32_t>(lo));
+  } else {
+    return __builtin_bit_cast(V, __builtin_amdgcn_ds_bpermute(j << 2, __builtin_bit_cast(int, v)));
+  }
+}
+
+// The half-tile walk of the packed kernels (sa2, sa1).  A wave's 64-centre batch is one flat
+// sequence of 32-row tiles; each tile takes the next two 16-row half tiles (centre, half) of the
+// batch in order, a centre having max(1, ceil(rows / 16)) of them.  The walk is wave-uniform
+// scalar state, so the tiles of steps t + 1 and t + 2 are named while tile t runs (the software
+// pipeline of the kernels).  Past the batch's last tile the walk names (last centre, half 0), a
+// valid half tile whose loads are issued like any other's and whose result nobody uses.
+struct HalfPair {
+  int jA, hA, jB, hB;  // first and second half tile; without a second one, the first again
+  bool live, hasB;     // the tile exists; its second half tile exists
+};
+template <typename NH>
+__device__ __forceinline__ HalfPair next_half_pair(int& js, int& hs, int& nhj, int ncen, NH nh_of) {
+  HalfPair t;
+  t.live = js < ncen;
+  if (!t.live) {
+    t.jA = t.jB = ncen - 1;
+    t.hA = t.hB = 0;
+    t.hasB = false;
+    return t;
+  }
+  t.jA = js;
+  t.hA = hs;
+  if (++hs >= nhj) {
+    hs = 0;
+    if (++js < ncen) nhj = nh_of(js);
+  }
+  t.hasB = js < ncen;
+  t.jB = t.hasB ? js : t.jA;
+  t.hB = t.hasB ? hs : t.hA;
+  if (t.hasB && ++hs >= nhj) {
+    hs = 0;
+    if (++js < ncen) nhj = nh_of(js);
+  }
+  return t;
+}
 
 template <int D, int C1, int C2>
 struct SaMfmaShape {
@@ -229,7 +297,9 @@ __global__ __launch_bounds__(kMfmaWaves * kWave) __attribute__((amdgpu_waves_per
   using Sh = SaMfmaShape<D, C1, C2>;
   constexpr int C0 = Sh::C0, KS = Sh::KS, MT = Sh::MT, CT = Sh::CT;
   __shared__ SaMfmaLds<D, C1, C2, PRE> L;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5, r32 = lane & 31;
+  const int tid = threadIdx.x, lane = tid & 63, h = lane >> 5, r32 = lane & 31;
+  // wave-uniform by construction; said so, the centre walk below stays in scalar registers and branches
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
 
   // ---- stage the weights (params: W1, b1, scale1, shift1, W2, b2, scale2, shift2) ---------
   const float* W1 = params;
@@ -310,17 +380,13 @@ __global__ __launch_bounds__(kMfmaWaves * kWave) __attribute__((amdgpu_waves_per
   }
   // The wave's centres are ql = q0, q0 + qs, ...: their metadata (order, count, centre) is
   // loaded 64 centres at a time, one per lane, and read back by readlane, so a centre's first
-  // tile waits only for its list entries (fetched one tile ahead) and its U rows.
-  auto lane_bcast = [](auto v, int j) {
-    if constexpr (sizeof(v) == 8) {
-      const int64_t u = __builtin_bit_cast(int64_t, v);
-      const int lo = __builtin_amdgcn_readlane(static_cast<int>(u & 0xFFFFFFFF), j);
-      const int hi = __builtin_amdgcn_readlane(static_cast<int>(u >> 32), j);
-      return __builtin_bit_cast(decltype(v), (static_cast<int64_t>(hi) << 32) | static_cast<uint32_t>(lo));
-    } else {
-      return __builtin_bit_cast(decltype(v), __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), j));
-    }
-  };
+  // tile waits for neither: the PRE paths run a three-stage software pipeline over the batch's flat
+  // tile sequence.  While tile t runs its MFMAs, the list entry of tile t + 2 is loaded, and the U
+  // row and point of tile t + 1 are gathered through the entry loaded one step earlier: into a
+  // second register set ahead of tile t's MFMAs on the packed path (sa2), the two sets alternating
+  // by a two-step unrolled loop; into the freed layer-1 registers during tile t's last MFMAs on the
+  // 32-row path (sa3).  The pipeline is primed at the start of every 64-centre batch and drains at
+  // its end; loads past the last tile go through a valid tile's indices and are dropped.
   for (int64_t qc = q0; qc < total; qc += 64 * qs) {
     const int64_t qm = qc + lane * qs;
     int m_b = 0, m_rows = 0;  // rows 0: no hit (the centre's output is 0)
@@ -377,49 +443,57 @@ __global__ __launch_bounds__(kMfmaWaves * kWave) __attribute__((amdgpu_waves_per
           for (int ct = 0; ct < CT; ++ct) run[ct] = fmaxf(run[ct], m[ct]);
         }
       };
-      while (js < ncen) {
-        const int jA = js, hA = hs;
-        if (++hs >= nhj) {
-          hs = 0;
-          if (++js < ncen) nhj = nh_of(js);
-        }
-        const bool hasB = js < ncen;
-        const int jB = hasB ? js : jA, hB = hasB ? hs : hA;
-        if (hasB && ++hs >= nhj) {
-          hs = 0;
-          if (++js < ncen) nhj = nh_of(js);
-        }
-        int zo = 0;
-        asm volatile("" : "+v"(zo));
-        const bool sB = r32 >= 16;  // this lane's point: row r32 of the tile
-        const int b = sB ? lane_bcast(m_b, jB) : lane_bcast(m_b, jA);
-        const int64_t fc = sB ? lane_bcast(m_fc, jB) : lane_bcast(m_fc, jA);
-        const int rows = sB ? lane_bcast(m_rows, jB) : lane_bcast(m_rows, jA);
-        const T cx = sB ? lane_bcast(m_cx, jB) : lane_bcast(m_cx, jA);
-        const T cy = sB ? lane_bcast(m_cy, jB) : lane_bcast(m_cy, jA);
-        const T cz = sB ? lane_bcast(m_cz, jB) : lane_bcast(m_cz, jA);
-        const int row = 16 * (sB ? hB : hA) + (r32 & 15);
-        const int n = rows == 0 ? 0 : list[fc * nsample + (row < rows ? row : 0)];
-        f32x16 acc1[MT];
+      // This lane's point is row r32 of the tile: its centre is the first or the second half tile's.
+      // The centre's metadata comes by one ds_bpermute per value through the selected lane index.
+      const bool sB = r32 >= 16;
+      struct Gathered {  // what a tile waits for: the accumulator start (its U row) and its point
+        f32x16 u[MT];
+        T px, py, pz;
+      };
+      // stage 1: the list entry of this lane's row.  A centre without hits reads no list entry: its
+      // lanes load the centre's own count instead (one load without a branch) and stage 2 takes
+      // point 0 for them.
+      auto entry = [&](const HalfPair& t) {
+        const int jl = sB ? t.jB : t.jA;
+        const int64_t fc = lane_gather(m_fc, jl);
+        const int rows = lane_gather(m_rows, jl);
+        const int row = 16 * (sB ? t.hB : t.hA) + (r32 & 15);
+        const int32_t* e = rows == 0 ? count + fc : list + fc * nsample + (row < rows ? row : 0);
+        return *e;
+      };
+      // stage 2: the U row and the point behind list entry ne
+      auto gather = [&](const HalfPair& t, int ne, Gathered& g) {
+        const int jl = sB ? t.jB : t.jA;
+        const int b = lane_gather(m_b, jl);
+        const int n = lane_gather(m_rows, jl) == 0 ? 0 : ne;
         const float4* ur = reinterpret_cast<const float4*>(U + b * ub + static_cast<int64_t>(n) * C1 + 4 * h);
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
           for (int i = 0; i < 4; ++i) {
             const float4 u = ur[8 * mt + 2 * i];
-            acc1[mt][4 * i] = u.x;
-            acc1[mt][4 * i + 1] = u.y;
-            acc1[mt][4 * i + 2] = u.z;
-            acc1[mt][4 * i + 3] = u.w;
+            g.u[mt][4 * i] = u.x;
+            g.u[mt][4 * i + 1] = u.y;
+            g.u[mt][4 * i + 2] = u.z;
+            g.u[mt][4 * i + 3] = u.w;
           }
         // (points in packed (x, y, z, pad) rows measured no faster here -- sa2 0.298 -> 0.306, sa3
         // 0.594 -> 0.597 ms, r5ae_sa_p4_bench.log: the U rows dominate the gather -- so the FE passes
         // the (B, 3, N) layout; load3 takes either)
-        T px, py, pz;
-        pts.load3(b, n, px, py, pz);
-        const float dx = static_cast<float>(px - cx);
-        const float dy = static_cast<float>(py - cy);
-        const float dz = static_cast<float>(pz - cz);
+        pts.load3(b, n, g.px, g.py, g.pz);
+      };
+      // stage 3: the tile's MFMAs, split-3 and maxima
+      auto compute = [&](const HalfPair& t, const Gathered& g) {
+        int zo = 0;
+        asm volatile("" : "+v"(zo));
+        const int jl = sB ? t.jB : t.jA;
+        const T cx = lane_gather(m_cx, jl), cy = lane_gather(m_cy, jl), cz = lane_gather(m_cz, jl);
+        f32x16 acc1[MT];
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) acc1[mt] = g.u[mt];
+        const float dx = static_cast<float>(g.px - cx);
+        const float dy = static_cast<float>(g.py - cy);
+        const float dz = static_cast<float>(g.pz - cz);
         const float x0 = h == 0 ? dx : dy, x1 = h == 0 ? dz : 0.0f;
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) {
@@ -456,14 +530,189 @@ __global__ __launch_bounds__(kMfmaWaves * kWave) __attribute__((amdgpu_waves_per
           mA[ct] = fmaxf(a0, __shfl_xor(a0, 32, kWave));
           mB[ct] = fmaxf(a1, __shfl_xor(a1, 32, kWave));
         }
-        fold(jA, mA);
-        if (hasB) fold(jB, mB);
-      }
+        fold(t.jA, mA);
+        if (t.hasB) fold(t.jB, mB);
+      };
+      auto next = [&]() { return next_half_pair(js, hs, nhj, ncen, nh_of); };
+      // prime: tiles 0 and 1 named, their list entries loaded, tile 0 gathered
+      HalfPair t0 = next(), t1 = next();
+      Gathered ga, gb;
+      int na = entry(t0), nb = entry(t1);  // the list entries alternate like the register sets
+      gather(t0, na, ga);
+      // one step: nuse is the list entry of tile t + 1 (loaded one step ago), nload takes tile t + 2's
+      auto step = [&](const Gathered& cur, Gathered& nxt, int nuse, int& nload) {
+        const HalfPair t2 = next();
+        nload = entry(t2);
+        gather(t1, nuse, nxt);
+        __builtin_amdgcn_sched_barrier(0);  // the loads above stay ahead of the tile's MFMAs
+        compute(t0, cur);
+        t0 = t1;
+        t1 = t2;
+      };
+      do {  // ncen >= 1: tile 0 exists
+        step(ga, gb, nb, na);
+        if (!t0.live) break;
+        step(gb, ga, na, nb);
+      } while (t0.live);
       if (runj >= 0) flush();
       continue;
     }
-    // The first list row of the next centre is fetched one tile ahead; a centre without hits runs
-    // no tile, so "next" is the next centre with hits (lane mask of the batch).
+    if constexpr (BZ) {
+      // 32-row tiles, one centre at a time (sa3).  The flat sequence is every tile of every centre
+      // with hits, in order (lane mask of the batch); a centre without hits runs no tile, reads no
+      // list entry and gets its zeros here.  Past the last tile the walk names the first tile of
+      // the last centre with hits.
+      // With two 16-register accumulator starts per tile a second register set costs a wave per SIMD
+      // (148 VGPRs, 3 waves), so this path keeps one set: tile t + 1's U row is loaded into layer
+      // 1's accumulator registers once tile t's last split-3 has read them, and arrives under the
+      // tile's last MFMAs and its maximum (128 VGPRs, 4 waves).  List entries still run two tiles
+      // ahead.
+      const uint64_t live_c = __ballot(lane < ncen && m_rows > 0);
+      for (uint64_t e = __ballot(lane < ncen && m_rows == 0); e; e &= e - 1) {
+        const int64_t fce = lane_bcast(m_fc, static_cast<int>(__builtin_ctzll(e)));
+#pragma unroll
+        for (int ct = 0; ct < CT; ++ct)
+          if (h == 0) out[fce * C2 + 32 * ct + r32] = 0.0f;
+      }
+      if (live_c == 0) continue;
+      const int jlast = 63 - static_cast<int>(__builtin_clzll(live_c));
+      struct Tile {
+        int j, n0;  // centre (lane of the batch) and first row
+        bool live;
+      };
+      int cj = static_cast<int>(__builtin_ctzll(live_c)), cn = 0;  // the next tile to name; cj 64: none left
+      auto next = [&]() {
+        Tile t;
+        t.live = cj < 64;
+        if (!t.live) {
+          t.j = jlast;
+          t.n0 = 0;
+          return t;
+        }
+        t.j = cj;
+        t.n0 = cn;
+        if (cn + 32 < lane_bcast(m_rows, cj)) {
+          cn += 32;
+        } else {
+          const uint64_t m = cj >= 63 ? 0ull : (live_c & (~0ull << (cj + 1)));
+          cj = m ? static_cast<int>(__builtin_ctzll(m)) : 64;
+          cn = 0;
+        }
+        return t;
+      };
+      struct Gathered {  // what a tile waits for: the accumulator start (its U row) and its point
+        f32x16 u[MT];
+        T px, py, pz;
+      };
+      // stage 1: the list entry of this lane's row (padded rows repeat the first hit); only centres
+      // with hits are named, so rows >= 1
+      auto entry = [&](const Tile& t) {
+        const int64_t fc = lane_bcast(m_fc, t.j);
+        const int row = t.n0 + r32;
+        return list[fc * nsample + (row < lane_bcast(m_rows, t.j) ? row : 0)];
+      };
+      // stage 2: the U row (channels (r&3) + 8(r>>2) + 4h of each 32-channel tile, one 32-channel
+      // tile per call) and the point behind list entry n
+      auto gather_u = [&](const Tile& t, int n, Gathered& g, int mt) {
+        const int b = lane_bcast(m_b, t.j);
+        const float4* ur = reinterpret_cast<const float4*>(U + b * ub + static_cast<int64_t>(n) * C1 + 4 * h);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const float4 u = ur[8 * mt + 2 * i];
+          g.u[mt][4 * i] = u.x;
+          g.u[mt][4 * i + 1] = u.y;
+          g.u[mt][4 * i + 2] = u.z;
+          g.u[mt][4 * i + 3] = u.w;
+        }
+      };
+      auto gather_p = [&](const Tile& t, int n, Gathered& g) { pts.load3(lane_bcast(m_b, t.j), n, g.px, g.py, g.pz); };
+      // The accumulators of layer 2 start from zero (an inline-constant C operand) and the bias is
+      // added once to the centre's maximum: max_i fl(a_i + b) = fl(max_i a_i + b) (rounding is
+      // monotone), then the ReLU (max_i relu(v_i) = relu(max_i v_i)).
+      float mx[CT];
+#pragma unroll
+      for (int ct = 0; ct < CT; ++ct) mx[ct] = -__builtin_huge_valf();
+      // stage 3: the tile's MFMAs, split-3 and maximum; the centre's row goes out after its last tile.
+      // refill(mt) is called once layer 1's registers of channel tile mt have been read for the last time.
+      auto compute = [&](const Tile& t, const Gathered& g, auto refill) {
+        // An opaque zero added to every LDS weight index: the fragments are re-read per tile
+        // (one ds_read per MFMA) instead of being hoisted out of the loop into ~100 registers.
+        int zo = 0;
+        asm volatile("" : "+v"(zo));
+        const T cx = lane_bcast(m_cx, t.j), cy = lane_bcast(m_cy, t.j), cz = lane_bcast(m_cz, t.j);
+        f32x16 acc1[MT];
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) acc1[mt] = g.u[mt];
+        const float dx = static_cast<float>(g.px - cx);
+        const float dy = static_cast<float>(g.py - cy);
+        const float dz = static_cast<float>(g.pz - cz);
+        const float x0 = h == 0 ? dx : dy, x1 = h == 0 ? dz : 0.0f;
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) {
+          acc1[mt] = __builtin_amdgcn_mfma_f32_32x32x2f32(L.wx[mt][0][lane + zo], x0, acc1[mt], 0, 0, 0);
+          acc1[mt] = __builtin_amdgcn_mfma_f32_32x32x2f32(L.wx[mt][1][lane + zo], x1, acc1[mt], 0, 0, 0);
+#pragma unroll
+          for (int r = 0; r < 16; ++r) acc1[mt][r] = acc1[mt][r] > 0.0f ? acc1[mt][r] : 0.0f;
+        }
+        f32x16 acc2[CT];
+#pragma unroll
+        for (int ct = 0; ct < CT; ++ct)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) acc2[ct][r] = 0.0f;
+#pragma unroll
+        for (int s = 0; s < Sh::KB; ++s) {
+          float x[8];
+#pragma unroll
+          for (int jj = 0; jj < 8; ++jj) x[jj] = acc1[s / 2][8 * (s % 2) + jj];
+          const Split3 a = split3(x);
+          if (s % 2 == 1) refill(s / 2);
+#pragma unroll
+          for (int ct = 0; ct < CT; ++ct)
+            acc2[ct] = mfma_split3(a, L.w2s[ct][s][0][lane + zo], L.w2s[ct][s][1][lane + zo], L.w2s[ct][s][2][lane + zo],
+                                   acc2[ct]);
+        }
+#pragma unroll
+        for (int ct = 0; ct < CT; ++ct)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) mx[ct] = fmaxf(mx[ct], acc2[ct][r]);
+        if (t.n0 + 32 >= lane_bcast(m_rows, t.j)) {
+          const int64_t fc = lane_bcast(m_fc, t.j);
+          // the two lane halves hold different points of the same channel
+#pragma unroll
+          for (int ct = 0; ct < CT; ++ct) {
+            const float m = fmaxf(fmaxf(mx[ct], __shfl_xor(mx[ct], 32, kWave)) + b2[ct], 0.0f);
+            if (h == 0) out[fc * C2 + 32 * ct + r32] = m;
+            mx[ct] = -__builtin_huge_valf();
+          }
+        }
+      };
+      // prime: tiles 0 and 1 named, their list entries loaded, tile 0 gathered
+      Tile t0 = next(), t1 = next();
+      Gathered g;
+      int na = entry(t0), nb = entry(t1);  // two registers, alternating by the two-step unrolled loop
+#pragma unroll
+      for (int mt = 0; mt < MT; ++mt) gather_u(t0, na, g, mt);
+      gather_p(t0, na, g);
+      // one step: nuse is the list entry of tile t + 1 (loaded one step ago), nload takes tile t + 2's
+      auto step = [&](int nuse, int& nload) {
+        const Tile t2 = next();
+        nload = entry(t2);
+        compute(t0, g, [&](int mt) {
+          gather_u(t1, nuse, g, mt);
+          if (mt == MT - 1) gather_p(t1, nuse, g);
+        });
+        t0 = t1;
+        t1 = t2;
+      };
+      do {  // live_c != 0: tile 0 exists
+        step(nb, na);
+        if (!t0.live) break;
+        step(na, nb);
+      } while (t0.live);
+      continue;
+    }
+    // (not PRE) The first list row of the next centre is fetched one tile ahead; a centre without hits
+    // runs no tile, so "next" is the next centre with hits (lane mask of the batch).
     const uint64_t live_c = __ballot(lane < ncen && m_rows > 0);
     auto next_live = [&](int j) {  // the first centre after j with hits, or 64
       const uint64_t m = j >= 63 ? 0ull : (live_c & (~0ull << (j + 1)));
@@ -649,7 +898,9 @@ __global__ __launch_bounds__(kMfmaWaves * kWave) void sa3_mfma_kernel(
   constexpr int KS = (C0 + 1) / 2;  // layer-1 k-steps: input channels (2 s, 2 s + 1) on lane halves (0, 1)
   static_assert(D == 0 || D == 3, "sa1 tables");
   __shared__ Sa3Lds L;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5, r32 = lane & 31;
+  const int tid = threadIdx.x, lane = tid & 63, h = lane >> 5, r32 = lane & 31;
+  // wave-uniform by construction; said so, the centre walk below stays in scalar registers and branches
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const float* W1 = params;
   const float* pb1 = W1 + C1 * C0;
   const float* ps1 = pb1 + C1;
@@ -705,16 +956,6 @@ __global__ __launch_bounds__(kMfmaWaves * kWave) void sa3_mfma_kernel(
     q0 = static_cast<int64_t>(blockIdx.x) * kMfmaWaves + wave;
     qs = static_cast<int64_t>(gridDim.x) * kMfmaWaves;
   }
-  auto lane_bcast = [](auto v, int j) {
-    if constexpr (sizeof(v) == 8) {
-      const int64_t u = __builtin_bit_cast(int64_t, v);
-      const int lo = __builtin_amdgcn_readlane(static_cast<int>(u & 0xFFFFFFFF), j);
-      const int hi = __builtin_amdgcn_readlane(static_cast<int>(u >> 32), j);
-      return __builtin_bit_cast(decltype(v), (static_cast<int64_t>(hi) << 32) | static_cast<uint32_t>(lo));
-    } else {
-      return __builtin_bit_cast(decltype(v), __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), j));
-    }
-  };
   for (int64_t qc = q0; qc < total; qc += 64 * qs) {
     // this lane's centre of the next 64: cloud, flat index, rows (0: no hit), coordinates
     const int64_t qm = qc + lane * qs;
@@ -750,44 +991,51 @@ __global__ __launch_bounds__(kMfmaWaves * kWave) void sa3_mfma_kernel(
         run = fmaxf(run, m);
       }
     };
-    while (js < ncen) {
-      const int jA = js, hA = hs;
-      if (++hs >= nhj) {
-        hs = 0;
-        if (++js < ncen) nhj = nh_of(js);
+    // The same three-stage pipeline over the batch's flat tile sequence as sa_mlp_mfma_kernel's
+    // packed path: list entry of tile t + 2, point (and normal) of tile t + 1, MFMAs of tile t.
+    const bool sB = r32 >= 16;  // this lane's row r32 of the tile: first or second half tile
+    struct Gathered {
+      T px, py, pz;
+      FT f0, f1;  // D == 3: feature channel 0, and channel 1 (lane half 0) or 2 (half 1)
+    };
+    // stage 1: padded rows repeat the first hit (:104-106).  A centre without hits reads no list
+    // entry: its lanes load the centre's own count instead (one load without a branch) and stage 2
+    // takes point 0 for them (discarded)
+    auto entry = [&](const HalfPair& t) {
+      const int jl = sB ? t.jB : t.jA;
+      const int64_t fc = lane_gather(m_fc, jl);
+      const int rows = lane_gather(m_rows, jl);
+      const int row = 16 * (sB ? t.hB : t.hA) + (r32 & 15);
+      const int32_t* e = rows == 0 ? count + fc : list + fc * nsample + (row < rows ? row : 0);
+      return *e;
+    };
+    auto gather = [&](const HalfPair& t, int ne, Gathered& g) {
+      const int jl = sB ? t.jB : t.jA;
+      const int b = lane_gather(m_b, jl);
+      const int n = lane_gather(m_rows, jl) == 0 ? 0 : ne;
+      pts.load3(b, n, g.px, g.py, g.pz);
+      if constexpr (D != 0) {
+        const FT* f = feat + b * fb + static_cast<int64_t>(n) * fn;
+        g.f0 = f[0];
+        g.f1 = h == 0 ? f[fd] : f[2 * fd];
       }
-      const bool hasB = js < ncen;
-      const int jB = hasB ? js : jA, hB = hasB ? hs : hA;
-      if (hasB && ++hs >= nhj) {
-        hs = 0;
-        if (++js < ncen) nhj = nh_of(js);
-      }
+    };
+    auto compute = [&](const HalfPair& t, const Gathered& g) {
       // opaque zero on the LDS indices: fragments re-read per tile, not hoisted into registers
       int zo = 0;
       asm volatile("" : "+v"(zo));
-      const bool sB = r32 >= 16;  // this lane's row r32 of the tile: first or second half tile
-      const int b = sB ? lane_bcast(m_b, jB) : lane_bcast(m_b, jA);
-      const int64_t fc = sB ? lane_bcast(m_fc, jB) : lane_bcast(m_fc, jA);
-      const int rows = sB ? lane_bcast(m_rows, jB) : lane_bcast(m_rows, jA);
-      const T cx = sB ? lane_bcast(m_cx, jB) : lane_bcast(m_cx, jA);
-      const T cy = sB ? lane_bcast(m_cy, jB) : lane_bcast(m_cy, jA);
-      const T cz = sB ? lane_bcast(m_cz, jB) : lane_bcast(m_cz, jA);
-      const int row = 16 * (sB ? hB : hA) + (r32 & 15);
-      // padded rows repeat the first hit (:104-106); a centre without hits reads point 0 (discarded)
-      const int n = rows == 0 ? 0 : list[fc * nsample + (row < rows ? row : 0)];
-      T px, py, pz;
-      pts.load3(b, n, px, py, pz);
-      const float dx = static_cast<float>(px - cx);
-      const float dy = static_cast<float>(py - cy);
-      const float dz = static_cast<float>(pz - cz);
+      const int jl = sB ? t.jB : t.jA;
+      const T cx = lane_gather(m_cx, jl), cy = lane_gather(m_cy, jl), cz = lane_gather(m_cz, jl);
+      const float dx = static_cast<float>(g.px - cx);
+      const float dy = static_cast<float>(g.py - cy);
+      const float dz = static_cast<float>(g.pz - cz);
       float x[KS];
       x[0] = h == 0 ? dx : dy;
       if constexpr (D == 0) {
         x[1] = h == 0 ? dz : 0.0f;
       } else {
-        const FT* f = feat + b * fb + static_cast<int64_t>(n) * fn;
-        x[1] = h == 0 ? dz : static_cast<float>(f[0]);
-        x[2] = static_cast<float>(h == 0 ? f[fd] : f[2 * fd]);
+        x[1] = h == 0 ? dz : static_cast<float>(g.f0);
+        x[2] = static_cast<float>(g.f1);
       }
       f32x16 a1;
 #pragma unroll
@@ -824,9 +1072,30 @@ __global__ __launch_bounds__(kMfmaWaves * kWave) void sa3_mfma_kernel(
       }
       mA = fmaxf(mA, __shfl_xor(mA, 32, kWave));
       mB = fmaxf(mB, __shfl_xor(mB, 32, kWave));
-      fold(jA, mA);
-      if (hasB) fold(jB, mB);
-    }
+      fold(t.jA, mA);
+      if (t.hasB) fold(t.jB, mB);
+    };
+    auto next = [&]() { return next_half_pair(js, hs, nhj, ncen, nh_of); };
+    // prime: tiles 0 and 1 named, their list entries loaded, tile 0 gathered
+    HalfPair t0 = next(), t1 = next();
+    Gathered ga, gb;
+    int na = entry(t0), nb = entry(t1);  // the list entries alternate like the register sets
+    gather(t0, na, ga);
+    // one step: nuse is the list entry of tile t + 1 (loaded one step ago), nload takes tile t + 2's
+    auto step = [&](const Gathered& cur, Gathered& nxt, int nuse, int& nload) {
+      const HalfPair t2 = next();
+      nload = entry(t2);
+      gather(t1, nuse, nxt);
+      __builtin_amdgcn_sched_barrier(0);  // the loads above stay ahead of the tile's MFMAs
+      compute(t0, cur);
+      t0 = t1;
+      t1 = t2;
+    };
+    do {  // ncen >= 1: tile 0 exists
+      step(ga, gb, nb, na);
+      if (!t0.live) break;
+      step(gb, ga, na, nb);
+    } while (t0.live);
     if (runj >= 0) flush();
   }
 }
