@@ -14,11 +14,10 @@
 // maskless), and the softmax and weighted mean finish in registers.
 #include "common.h"
 #include "cpg_grid.h"
+#include "split3.h"
 
 namespace dvcp {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 // DVCP_CPG_SPLIT3 (default): conv1 on the bf16 matrix cores (v_mfma_f32_16x16x32_bf16) with the
 // fp32-accurate three-way split of sa_mlp_mfma.hip: each 8-channel quarter of the cost volume is
@@ -40,22 +39,7 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 #define DVCP_CPG_C2 2
 #endif
 
-// x = x0 + x1 + x2 exactly (bf16 pieces, as sa_mlp_mfma.hip's split3)
-__device__ __forceinline__ void cpg_split3(float x, __bf16& p0, __bf16& p1, __bf16& p2) {
-  p0 = static_cast<__bf16>(x);
-  const float r1 = x - static_cast<float>(p0);
-  p1 = static_cast<__bf16>(r1);
-  p2 = static_cast<__bf16>(r1 - static_cast<float>(p1));
-}
-__device__ __forceinline__ f32x4 cpg_mfma_split3(const bf16x8& a0, const bf16x8& a1, const bf16x8& a2,
-                                                const bf16x8& b0, const bf16x8& b1, const bf16x8& b2, f32x4 acc) {
-  acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a2, b0, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, b1, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, b2, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, b0, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, b1, acc, 0, 0, 0);
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, b0, acc, 0, 0, 0);
-}
+// conv1 runs on the bf16 matrix cores through the three-way split of csrc/split3.h
 
 // DVCP_CPG_DIAG (diagnostic builds only): wave 0 of each workgroup records the shader clock at the
 // phase boundaries and writes the deltas over the key point's softmax weights (tools/cpg_diag.py).
@@ -215,7 +199,7 @@ __global__ __launch_bounds__(kCpgThreads) void cpg_kernel(const float* __restric
         for (int jj = 0; jj < 8; ++jj) {
           const float w = tap < 27 ? P1[(co * 32 + kCpgQ * q + jj) * 27 + tap] : 0.0f;
           __bf16 x0, x1, x2;
-          cpg_split3(w, x0, x1, x2);
+          split3(w, x0, x1, x2);
           b0[jj] = x0;
           b1[jj] = x1;
           b2[jj] = x2;
@@ -234,7 +218,7 @@ __global__ __launch_bounds__(kCpgThreads) void cpg_kernel(const float* __restric
         const int g = l >> 5, fp = l & 31;
         const float d = sv[fp] - t;
         __bf16 x0, x1, x2;
-        cpg_split3(d * d, x0, x1, x2);
+        split3(d * d, x0, x1, x2);
         const int c8 = cpg_halo(g, dG, dGG, PG, PGG) * 8 + (fp & 7);
         vh[c8] = __builtin_bit_cast(uint16_t, x0);
         vh[8 * PV + c8] = __builtin_bit_cast(uint16_t, x1);
@@ -281,7 +265,7 @@ __global__ __launch_bounds__(kCpgThreads) void cpg_kernel(const float* __restric
             const bf16x8 a0 = __builtin_bit_cast(bf16x8, vsp[cell]);
             const bf16x8 a1 = __builtin_bit_cast(bf16x8, vsp[PV + cell]);
             const bf16x8 a2 = __builtin_bit_cast(bf16x8, vsp[2 * PV + cell]);
-            acc[i] = cpg_mfma_split3(a0, a1, a2, b0, b1, b2, acc[i]);
+            acc[i] = mfma_split3(a0, a1, a2, b0, b1, b2, acc[i]);
           }
       }
     }

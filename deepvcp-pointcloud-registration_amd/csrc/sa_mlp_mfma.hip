@@ -40,11 +40,9 @@
 // are those of the unpipelined loop, which the plain (not PRE) path still runs.
 #include "common.h"
 #include "morton.h"
+#include "split3.h"
 
 namespace dvcp {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 #ifndef DVCP_SA_SPLIT3
 #define DVCP_SA_SPLIT3 1
@@ -54,34 +52,7 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 #define DVCP_SA_PACK16 1
 #endif
 
-// x = x0 + x1 + x2 exactly (bf16 pieces of eight fp32 values; see the header)
-struct Split3 {
-  bf16x8 p0, p1, p2;
-};
-__device__ __forceinline__ Split3 split3(const float (&x)[8]) {
-  Split3 s;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const __bf16 b0 = static_cast<__bf16>(x[j]);
-    const float r1 = x[j] - static_cast<float>(b0);
-    const __bf16 b1 = static_cast<__bf16>(r1);
-    const float r2 = r1 - static_cast<float>(b1);
-    s.p0[j] = b0;
-    s.p1[j] = b1;
-    s.p2[j] = static_cast<__bf16>(r2);
-  }
-  return s;
-}
-// acc += a.b over one 16-deep k-step, the six significant piece products, smallest first
-__device__ __forceinline__ f32x16 mfma_split3(const Split3& a, const bf16x8& b0, const bf16x8& b1, const bf16x8& b2,
-                                             f32x16 acc) {
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.p2, b0, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.p1, b1, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.p0, b2, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.p1, b0, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.p0, b1, acc, 0, 0, 0);
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.p0, b0, acc, 0, 0, 0);
-}
+// split3 / mfma_split3: csrc/split3.h (the split written on register pairs)
 
 constexpr int kMfmaWaves = 4;  // centres in flight per workgroup (one per SIMD)
 
@@ -144,6 +115,82 @@ __device__ __forceinline__ HalfPair next_half_pair(int& js, int& hs, int& nhj, i
     if (++js < ncen) nhj = nh_of(js);
   }
   return t;
+}
+
+// ReLU of an accumulator register, max(x, +0) with a NaN giving 0 like `x > 0 ? x : 0`.  Written as
+// fmaxf or as that select, the compiler puts a canonicalising v_max_f32 x, x in front of the
+// v_max_f32 (it cannot see that an MFMA result is already canonical): two instructions per
+// register, 32 + 32 per sa3 tile.  v_med3_f32(x, 0, +inf) is one, with the same result for every
+// input (a NaN operand makes it min3, which skips the NaN: 0).
+__device__ __forceinline__ float sa_relu(float x) {
+  // +inf through an opaque scalar register: with both bounds visible the compiler folds the
+  // median back into the two-instruction maximum
+  float inf = __builtin_inff();
+  asm("" : "+s"(inf));
+  return __builtin_amdgcn_fmed3f(x, 0.0f, inf);
+}
+
+// Layer 2 of one tile on the split-3 bf16 MFMAs: acc2[ct] += H1 . W2^T over the 2 MT k-steps, the A
+// operand of k-step s being layer 1's accumulator registers 8 (s % 2) .. + 7 of tile s / 2.
+// Products and their order are mfma_split3's, k-step by k-step, tile ct 0 then 1, in both forms.
+// w2(ct, s, piece): the B fragment; refill(mt): called once layer 1's registers of channel tile
+// mt have been read for the last time.
+//
+// AHEAD = false (sa2): each k-step is split, then multiplied.  The compiler emits a k-step as a
+// burst of ~45 VALU followed by its 12 MFMAs; the waves of a SIMD overlap each other's bursts.
+//
+// AHEAD = true (sa3): an MFMA holds the vector issue port for 8 of its 32 cycles, and a wave fits
+// about six VALU instructions into each gap.  The split of k-step s + 1 (Split3Stages: 12 stages
+// of at most 5 instructions) is placed stage by stage behind the 12 MFMAs of k-step s; a
+// scheduling barrier after each MFMA keeps VALU and MFMA instructions from crossing it (LDS and
+// global loads, scalar code and waits stay free to move), so only k-step 0's split runs outside
+// the MFMAs' shadow.  (`sched_group_barrier` groups alone left the emitted burst / cluster order
+// as it was.)  The wave raises its priority over each k-step's MFMAs, so that the other waves'
+// split bursts do not delay the chain it interleaves with.  The next pieces live beside the
+// current ones: 132 VGPRs, three waves per SIMD.  Measured: sa3 faster
+// with both together, with neither alone; sa2 with neither (and its 4-wave form then spills).
+constexpr int kSchedPinVectorAlu = 0x4 | 0x10 | 0x20 | 0x40 | 0x80 | 0x100 | 0x200;  // all but VALU, MFMA, TRANS may cross
+template <int MT, int CT, bool AHEAD, typename W2, typename Refill>
+__device__ __forceinline__ void sa_layer2(const f32x16 (&acc1)[MT], f32x16 (&acc2)[CT], W2 w2, Refill refill) {
+  static_assert(6 * CT == Split3Stages::kStages, "one stage of the next split per MFMA of a k-step");
+  constexpr int KB = 2 * MT;
+  Split3Stages sp;
+  auto stage = [&](int s, int i) {  // stage i of k-step s's split
+    const int r = 8 * (s % 2) + 2 * (i / 3);
+    sp.stage(i, acc1[s / 2][r], acc1[s / 2][r + 1]);
+  };
+  if (AHEAD) {
+#pragma unroll
+    for (int i = 0; i < Split3Stages::kStages; ++i) stage(0, i);
+  }
+#pragma unroll
+  for (int s = 0; s < KB; ++s) {
+    Split3 a;
+    if (AHEAD) {
+      a = sp.pieces();
+    } else {
+      float x[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) x[j] = acc1[s / 2][8 * (s % 2) + j];
+      a = split3(x);
+      if (s % 2 == 1) refill(s / 2);
+    }
+    if (AHEAD) __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+    for (int ct = 0; ct < CT; ++ct) {
+      const bf16x8 b0 = w2(ct, s, 0), b1 = w2(ct, s, 1), b2 = w2(ct, s, 2);
+#pragma unroll
+      for (int m = 0; m < 6; ++m) {
+        acc2[ct] = mfma_split3_product(m, a, b0, b1, b2, acc2[ct]);
+        if (AHEAD && s + 1 < KB) {
+          stage(s + 1, 6 * ct + m);
+          __builtin_amdgcn_sched_barrier(kSchedPinVectorAlu);
+        }
+      }
+    }
+    if (AHEAD) __builtin_amdgcn_s_setprio(0);
+    if (AHEAD && s % 2 == 0) refill(s / 2);  // k-step s + 1, the last reader of tile s / 2, is split
+  }
 }
 
 template <int D, int C1, int C2>
@@ -288,8 +335,12 @@ __global__ __launch_bounds__(kBuildThreads) void sa_order_kernel(PointsView<T> c
   morton_sort(S, get, [&](int pos, int i, const float (&)[3]) { o[pos] = i; }, lo, hi, bins, wsum);
 }
 
+// Waves per SIMD asked of the compiler: the packed kernel (sa2) is held at four (left at "three or
+// more" it takes 132 VGPRs once the split's subtractions stay scalar; held, the fp32 instance fits
+// 128 without scratch, the fp64-coordinate one spills one 8-byte loop invariant outside the tile
+// loop); the others take what they need (sa3: 132 VGPRs, three waves, see sa_layer2).
 template <typename T, int D, int C1, int C2, bool PRE, bool PACK = false>
-__global__ __launch_bounds__(kMfmaWaves * kWave) __attribute__((amdgpu_waves_per_eu(3))) void sa_mlp_mfma_kernel(
+__global__ __launch_bounds__(kMfmaWaves * kWave) __attribute__((amdgpu_waves_per_eu(PACK ? 4 : 3))) void sa_mlp_mfma_kernel(
     PointsView<T> pts, PointsView<T> ctr, int S, int B, const float* __restrict__ feat, int64_t fb, int64_t fn,
     const int32_t* __restrict__ count, const int32_t* __restrict__ list, int nsample,
     const float* __restrict__ params, const float* __restrict__ U, int64_t ub, const int32_t* __restrict__ order,
@@ -500,24 +551,14 @@ __global__ __launch_bounds__(kMfmaWaves * kWave) __attribute__((amdgpu_waves_per
           acc1[mt] = __builtin_amdgcn_mfma_f32_32x32x2f32(L.wx[mt][0][lane + zo], x0, acc1[mt], 0, 0, 0);
           acc1[mt] = __builtin_amdgcn_mfma_f32_32x32x2f32(L.wx[mt][1][lane + zo], x1, acc1[mt], 0, 0, 0);
 #pragma unroll
-          for (int r = 0; r < 16; ++r) acc1[mt][r] = acc1[mt][r] > 0.0f ? acc1[mt][r] : 0.0f;
+          for (int r = 0; r < 16; ++r) acc1[mt][r] = sa_relu(acc1[mt][r]);
         }
         f32x16 acc2[CT];
 #pragma unroll
         for (int ct = 0; ct < CT; ++ct)
 #pragma unroll
           for (int r = 0; r < 16; ++r) acc2[ct][r] = 0.0f;
-#pragma unroll
-        for (int st = 0; st < Sh::KB; ++st) {
-          float x[8];
-#pragma unroll
-          for (int jj = 0; jj < 8; ++jj) x[jj] = acc1[st / 2][8 * (st % 2) + jj];
-          const Split3 a = split3(x);
-#pragma unroll
-          for (int ct = 0; ct < CT; ++ct)
-            acc2[ct] = mfma_split3(a, L.w2s[ct][st][0][lane + zo], L.w2s[ct][st][1][lane + zo],
-                                   L.w2s[ct][st][2][lane + zo], acc2[ct]);
-        }
+        sa_layer2<MT, CT, false>(acc1, acc2, [&](int ct, int st, int pc) { return L.w2s[ct][st][pc][lane + zo]; }, [](int) {});
         float mA[CT], mB[CT];
 #pragma unroll
         for (int ct = 0; ct < CT; ++ct) {
@@ -652,25 +693,14 @@ __global__ __launch_bounds__(kMfmaWaves * kWave) __attribute__((amdgpu_waves_per
           acc1[mt] = __builtin_amdgcn_mfma_f32_32x32x2f32(L.wx[mt][0][lane + zo], x0, acc1[mt], 0, 0, 0);
           acc1[mt] = __builtin_amdgcn_mfma_f32_32x32x2f32(L.wx[mt][1][lane + zo], x1, acc1[mt], 0, 0, 0);
 #pragma unroll
-          for (int r = 0; r < 16; ++r) acc1[mt][r] = acc1[mt][r] > 0.0f ? acc1[mt][r] : 0.0f;
+          for (int r = 0; r < 16; ++r) acc1[mt][r] = sa_relu(acc1[mt][r]);
         }
         f32x16 acc2[CT];
 #pragma unroll
         for (int ct = 0; ct < CT; ++ct)
 #pragma unroll
           for (int r = 0; r < 16; ++r) acc2[ct][r] = 0.0f;
-#pragma unroll
-        for (int s = 0; s < Sh::KB; ++s) {
-          float x[8];
-#pragma unroll
-          for (int jj = 0; jj < 8; ++jj) x[jj] = acc1[s / 2][8 * (s % 2) + jj];
-          const Split3 a = split3(x);
-          if (s % 2 == 1) refill(s / 2);
-#pragma unroll
-          for (int ct = 0; ct < CT; ++ct)
-            acc2[ct] = mfma_split3(a, L.w2s[ct][s][0][lane + zo], L.w2s[ct][s][1][lane + zo], L.w2s[ct][s][2][lane + zo],
-                                   acc2[ct]);
-        }
+        sa_layer2<MT, CT, true>(acc1, acc2, [&](int ct, int st, int pc) { return L.w2s[ct][st][pc][lane + zo]; }, refill);
 #pragma unroll
         for (int ct = 0; ct < CT; ++ct)
 #pragma unroll
@@ -1047,7 +1077,7 @@ __global__ __launch_bounds__(kMfmaWaves * kWave) void sa3_mfma_kernel(
       for (int s = 0; s < KS; ++s) a1 = __builtin_amdgcn_mfma_f32_32x32x2f32(L.w1[s][lane + zo], x[s], a1, 0, 0, 0);
       float v[8];
 #pragma unroll
-      for (int r = 0; r < 8; ++r) v[r] = fmaxf(a1[r], 0.0f);
+      for (int r = 0; r < 8; ++r) v[r] = sa_relu(a1[r]);
       const Split3 p1 = split3(v);
       f32x16 a2;
 #pragma unroll
@@ -1058,7 +1088,7 @@ __global__ __launch_bounds__(kMfmaWaves * kWave) void sa3_mfma_kernel(
       const Split3 w2{L.w2[0][lane + zo], L.w2[1][lane + zo], L.w2[2][lane + zo]};
       a2 = mfma_split3(w2, p1.p0, p1.p1, p1.p2, a2);
 #pragma unroll
-      for (int r = 0; r < 8; ++r) v[r] = fmaxf(a2[r], 0.0f);
+      for (int r = 0; r < 8; ++r) v[r] = sa_relu(a2[r]);
       const Split3 p2 = split3(v);
       f32x16 a3;
 #pragma unroll

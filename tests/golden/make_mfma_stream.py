@@ -1,0 +1,196 @@
+"""Fixture of the split-3 MFMA kernels' outputs (tests/test_gpu_mfma_stream.py).
+
+Run once on the GPU at the commit whose arithmetic is the yardstick:
+
+    python tests/golden/make_mfma_stream.py [out.npz]   # default: tests/golden/mfma_stream.npz
+
+The kernels of csrc/sa_mlp_mfma.hip, csrc/dfe_mfma.hip and csrc/cpg.hip feed the bf16 matrix cores
+with three-piece splits of fp32 values; a change of their instruction stream must leave every
+output bit as it was.  This module builds the seeded inputs (shared with the test, which imports
+it) and records the outputs of
+
+  * ops.sa_group_mlp (sa1, sa2) and ops.sa_group_mlp_rows (sa3) on the hand-built lists of
+    tests/test_gpu_sa_pipeline.py (counts cycling through 0, 1, 15, 16, 17, 31, 32, 33, 63, 64 and
+    nsample; B = 8 with S = N = 2100, B = 3 with 5600),
+  * ops.dfe_tgt collapsed, literal and on the fp16 table, on the shapes of the test's permutation
+    cases,
+  * ops.cpg (corresponding point and softmax weights).
+
+Features are `wide`: magnitudes 2^-20 .. 2^20 with both signs, exact zeros, values that are exact
+in one or two bf16 pieces (second / third piece zero) and values near 2^-120 whose second and
+third pieces are subnormal.
+
+The full outputs are 1 - 4 MB each, over the size a committed file may have, so an output is
+recorded as the SHA-256 of its bytes plus every `step`-th row (at most 64 rows) for a readable
+diff; arrays of at most 4096 elements are kept whole.  Equal digests are equal bytes, which is what
+torch.equal asks apart from the sign of a zero, where the digest is the stricter of the two.  The
+digests of the inputs are recorded too, so a changed random stream shows as such and not as a
+kernel difference.
+"""
+import hashlib
+import os
+import sys
+
+import numpy as np
+import torch
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+TESTS = os.path.dirname(HERE)
+ROOT = os.path.dirname(TESTS)
+for _p in (ROOT, os.path.join(ROOT, "deepvcp-pointcloud-registration_amd"), TESTS):
+    if _p not in sys.path:
+        sys.path.insert(0, _p)
+
+PATH = os.path.join(HERE, "mfma_stream.npz")
+
+SA_CASES = [(table, shape) for table in (0, 1, 2) for shape in ("flat", "xcd")]
+# B, M, Q: fewer candidates than the DFE pipeline's depth, one past its unroll of 8, the
+# XCD-mapped grid (B % 8 == 0), the flat grid of 512 workgroups with a ragged last round
+DFE_CASES = [(1, 40, 1), (1, 40, 5), (1, 40, 9), (8, 900, 257), (3, 900, 700)]
+CPG_CASES = [(1, 1, 1.0), (1, 3, 1.0), (2, 8, 1.0), (1, 3, 2.0)]  # B, K key points, search radius
+
+
+def wide(shape, g, emax=20):
+    """fp32 values of magnitude 2^-emax .. 2^emax, both signs, with the special classes of the
+    module docstring mixed in (5 % zeros, 10 % one-piece, 10 % two-piece, 5 % near 2^-120)."""
+    n = int(np.prod(shape))
+    e = torch.randint(-emax, emax + 1, (n,), generator=g).float()
+    mant = 1.0 + torch.randint(0, 1 << 23, (n,), generator=g).float() * 2.0 ** -23
+    sign = 1.0 - 2.0 * torch.randint(0, 2, (n,), generator=g).float()
+    x = sign * mant * torch.exp2(e)
+    u = torch.randint(0, 100, (n,), generator=g)
+    one = x.bfloat16().float()
+    two = one + (x - one).bfloat16().float()
+    x = torch.where(u < 5, torch.zeros_like(x), x)
+    x = torch.where((u >= 5) & (u < 15), one, x)
+    x = torch.where((u >= 15) & (u < 25), two, x)
+    x = torch.where((u >= 25) & (u < 30), x * 2.0 ** -118 * torch.exp2(-e), x)
+    return x.view(*shape)
+
+
+def sa_inputs(table, shape):
+    """test_gpu_sa_pipeline's model and hand-built lists for one table, with `wide` features."""
+    import test_gpu_sa_pipeline as T
+    B, S, N = T.SHAPES[shape]
+    c = T._make(table, B, S, N, None, rows_variant=(table == 2), seed=500 + 10 * table + B)
+    if c["feat"] is not None:
+        c["feat"] = wide(tuple(c["feat"].shape), torch.Generator().manual_seed(7000 + 10 * table + B))
+    return c
+
+
+def sa_run(c, dev):
+    import test_gpu_sa_pipeline as T
+    return T._run(c, dev)
+
+
+def dfe_model(dev):
+    import dvcp
+    torch.manual_seed(5)
+    return dvcp.feat_embedding_layer().eval().to(dev)
+
+
+def dfe_inputs(B, M, Q, wide_feat, seed=0):
+    """CPU inputs of one target-DFE case: points and candidates in [-1, 1)^3, features `wide` or
+    standard normal."""
+    g = torch.Generator().manual_seed(8000 + 100 * B + Q + seed)
+    ref_xyz = (torch.rand(B, M, 3, generator=g, dtype=torch.float64) * 2 - 1).float()
+    qry = (torch.rand(B, Q, 3, generator=g, dtype=torch.float64) * 2 - 1).float()
+    feat = wide((B, M, 32), g) if wide_feat else torch.randn(B, M, 32, generator=g)
+    return ref_xyz, feat, qry
+
+
+def dfe_run(model, ref_xyz, feat, qry, dev):
+    """{collapsed, literal, f16} outputs (B, Q, 32) of one case; the fp16 table holds the features
+    scaled by 2^-8 (2^20 is past fp16's range)."""
+    from dvcp import ops
+    x, f, q = ref_xyz.to(dev), feat.to(dev), qry.to(dev)
+    dist, idx, _ = ops.knn(x, q, 32, ref_pdim=1, qry_pdim=1)
+    p = model.packed_params()
+    out = {"collapsed": ops.dfe_tgt(x, f, q, dist, idx, p, ref_pdim=1),
+           "literal": ops.dfe_tgt(x, f, q, dist, idx, p, ref_pdim=1, literal=True),
+           "f16": ops.dfe_tgt(x, (f * 2.0 ** -8).half(), q, dist, idx, p, ref_pdim=1)}
+    torch.cuda.synchronize()
+    return {k: v.cpu() for k, v in out.items()}
+
+
+def cpg_model(dev):
+    import dvcp
+    torch.manual_seed(6)
+    return dvcp.cpg().eval().to(dev)
+
+
+def cpg_inputs(B, K, r):
+    G = int(2 * r / 0.4 + 1)
+    C = G ** 3
+    g = torch.Generator().manual_seed(9000 + 100 * B + 10 * K + G)
+    src = wide((B, K, 1, 32), g, emax=3)
+    tgt = wide((B, K, C, 32), g, emax=3).permute(0, 1, 3, 2)  # the reference's permuted view
+    cand = torch.randn(B, K, C, 3, generator=g)
+    return src, tgt, cand, G
+
+
+def cpg_run(model, src, tgt, cand, G, dev):
+    from dvcp import ops
+    vcp, w = ops.cpg(src.to(dev), tgt.to(dev), cand.to(dev), G, model.packed_params(), want_weight=True)
+    torch.cuda.synchronize()
+    return {"vcp": vcp.cpu(), "w": w.cpu()}
+
+
+def digest(t):
+    a = np.ascontiguousarray(t.detach().cpu().numpy())
+    return np.frombuffer(hashlib.sha256(a.tobytes()).digest(), dtype=np.uint8).copy()
+
+
+def record(t):
+    """What the fixture keeps of an output: (digest, rows kept, their stride)."""
+    a = np.ascontiguousarray(t.detach().cpu().numpy())
+    if a.size <= 4096:
+        return digest(t), a, 1
+    rows = a.reshape(-1, a.shape[-1])
+    step = max(1, -(-rows.shape[0] // 64))
+    return digest(t), rows[::step].copy(), step
+
+
+def sample(t, step):
+    a = np.ascontiguousarray(t.detach().cpu().numpy())
+    return a if step == 1 and a.size <= 4096 else a.reshape(-1, a.shape[-1])[::step]
+
+
+def all_outputs(dev):
+    """name -> (output tensor, tuple of its input tensors), every case of the fixture."""
+    res = {}
+    for table, shape in SA_CASES:
+        c = sa_inputs(table, shape)
+        ins = [c["xyz"], c["ctr"], c["count"], c["lst"]] + [c[k] for k in ("feat", "rows") if c[k] is not None]
+        res[f"sa{table + 1}_{shape}"] = (sa_run(c, dev), ins)
+    m = dfe_model(dev)
+    for B, M, Q in DFE_CASES:
+        ins = dfe_inputs(B, M, Q, wide_feat=True)
+        for k, v in dfe_run(m, *ins, dev).items():
+            res[f"dfe_{k}_B{B}_Q{Q}"] = (v, list(ins))
+    m = cpg_model(dev)
+    for B, K, r in CPG_CASES:
+        src, tgt, cand, G = cpg_inputs(B, K, r)
+        for k, v in cpg_run(m, src, tgt, cand, G, dev).items():
+            res[f"cpg_{k}_B{B}_K{K}_G{G}"] = (v, [src, tgt, cand])
+    return res
+
+
+def main():
+    dev = torch.device("cuda:0")
+    z = {}
+    for name, (out, ins) in all_outputs(dev).items():
+        d, rows, step = record(out)
+        z[name + "::sha256"] = d
+        z[name + "::rows"] = rows
+        z[name + "::step"] = np.int64(step)
+        z[name + "::inputs"] = np.stack([digest(t) for t in ins])
+        print(f"{name}: shape {tuple(out.shape)} finite {bool(torch.isfinite(out).all())} "
+              f"max|x| {float(out.abs().max()):.3e} rows kept {rows.shape}", flush=True)
+    path = sys.argv[1] if len(sys.argv) > 1 else PATH
+    np.savez_compressed(path, **z)
+    print(f"wrote {path}: {os.path.getsize(path)} bytes")
+
+
+if __name__ == "__main__":
+    main()
