@@ -5,8 +5,9 @@
 // Why: the brute-force scan meets reference points in index order, so a lane keeps inserting into
 // its sorted top-32 and the wave executes the 32-deep insertion network on almost every point.
 // Here both sets are sorted by a 12-bit Morton cell, references into 64-point tiles with boxes.
-// Each wave takes 64 Morton-consecutive queries (a compact box), sorts the tiles by the lower
-// bound of the distance between its query box and each tile box, and scans tiles nearest first:
+// Each wave takes 64 Morton-consecutive queries (a compact box), orders the tiles by the lower
+// bound of the distance between its query box and each tile box (k <= 16: a bitonic sort; k > 16:
+// a counting sort into buckets of the bound, knn_wave_order), and scans tiles nearest first:
 //   * tile data is wave-uniform, so points come through the scalar cache as SGPR operands;
 //   * a tile is skipped when no lane's own lower bound reaches its current k-th distance;
 //   * the scan stops when the next tile's bound exceeds every lane's k-th distance.
@@ -525,8 +526,9 @@ __global__ __launch_bounds__(kTiledThreads) void knn_tiled_query_kernel(const fl
 
 
 // ---------------------------------------------------------------------------------------------
-// Buffered selection (k in 17..32; the forward's k = 32).  Same tiles, wave-ordered scan, pruning
-// and stop rule as knn_tiled_query_kernel, but a lane no longer inserts each candidate into its
+// Buffered selection (k in 17..32; the forward's k = 32).  Same tiles and per-lane pruning as
+// knn_tiled_query_kernel, with the wave's tile order from knn_wave_order below (buckets of the
+// lower bound behind a certified bound, not a sort), and a lane no longer inserts each candidate into its
 // sorted top-32 as it appears (a 32-slot insertion network that the whole wave executes for every
 // point that is a candidate for ANY lane: ~220 such steps per wave at C3, the kernel's cost).
 // Instead each lane appends its own candidates -- (d2, index) keys below its current k-th key --
@@ -538,26 +540,20 @@ __global__ __launch_bounds__(kTiledThreads) void knn_tiled_query_kernel(const fl
 // Exactness is unchanged: the merged list is always the 32 smallest (d2, index) keys of every
 // point appended, and a point is only left out when its key is not below a k-th key that is at
 // least the true one (filters and pruning use the last merged, i.e. a stale-high, k-th key).
-// DVCP_KNN_SORD: the sorted tile order in LDS (default); DVCP_KNN_STAGE_OUT: coalesced output rows
-#ifndef DVCP_KNN_SORD
-#define DVCP_KNN_SORD 1
-#endif
+// DVCP_KNN_STAGE_OUT: coalesced output rows
 #ifndef DVCP_KNN_STAGE_OUT
 #define DVCP_KNN_STAGE_OUT 2
 #endif
 constexpr int kSelBufN = 16;   // buffer capacity per lane (>= kTile: a merge makes room for a whole tile)
 constexpr int kSelSortN = 16;
-constexpr int kSordWords = (kMaxTiles + 2) / 3;  // a wave's sorted tile order, three 10-bit ids per word
+constexpr int kSordWords = (kMaxTiles + 2) / 3;  // a wave's tile order, three 10-bit ids per word
 // A tile's 256 bytes are loaded once some lane is known to need it (prefetching one sorted position
 // ahead made every scanned tile wait for its successor's load at the loop latch, ~660 clk per
 // skipped tile under DVCP_KNN_DIAG; round 3).
-// DVCP_KNN_CHUNK (default): the sorted order is scanned 64 positions at a time behind a
-// tile-parallel prefilter against lane-group boxes (see the scan below).
+// The order is scanned 64 positions at a time behind a tile-parallel prefilter against lane-group
+// boxes (see the scan below).
 // (Round 4 measured an exact per-lane bulk test over each 64-position chunk -- every lane's tile
 // box against all 64 queries of the wave -- 0.92 against 0.75 ms per C3 batch: not kept.)
-#ifndef DVCP_KNN_CHUNK
-#define DVCP_KNN_CHUNK 1
-#endif
 // (Round 4 also measured issuing the tile loads of 2 or 3 surviving positions together before
 // their visits: 0.77 / 0.83 against 0.76 ms -- the scan is not waiting on those loads.)
 // DVCP_KNN_SLOAD: an active tile's 16 points reach the wave as scalar loads (the tile index is
@@ -599,6 +595,185 @@ __device__ __forceinline__ void key_ce(uint32_t& ah, uint32_t& al, uint32_t& bh,
   bl = sw ? tl : bl;
 }
 
+// ---------------------------------------------------------------------------------------------
+// The wave's tile order (knn_sel_query_kernel): a certified bound and two counting passes instead
+// of a 1024-key bitonic sort.  The selection is exact for any visit order as long as no tile that
+// can hold one of a lane's 32 nearest keys is left out; the order only makes the k-th distances
+// converge early and carries the stop rule, so a bucket order is enough.
+//
+// Certificate.  ub(tile) is the far-corner distance between the wave's query box and the tile's
+// outward-rounded half box, in the d2 expression's own shape: per axis f = max(fl(bh - wl),
+// fl(wh - bl)) >= |fl(p - q)| for every point p of the tile and query q of the wave (rounding is
+// monotone), so (fx*fx + fy*fy) + fz*fz, rounded the same way, is >= every computed d2; the
+// (1 + 2^-20) margin on top pays for nothing the argument needs (as bq_prune_thr's).  A tile
+// certifies when all its 16 slots are real points and its box is finite.  B0, the second smallest
+// certified ub, then bounds the 32nd key of every live lane from above: two tiles, 32 points.  B0
+// is +inf (nothing dropped) when fewer than two tiles certify (M < 32 among them) or a
+// live query is not finite.
+//
+// Order.  A tile with lb > B0 is dropped: every computed d2 in it is above every lane's 32nd key,
+// ties included.  The others are counting-sorted by knn_bucket(lb, top), the one expression
+// used here and by the scan's stop rule; it is monotone in lb, so bucket(lb) > bucket(x) implies
+// lb > x.  Inside a bucket the order is whatever the LDS adds return.
+// (Starting every lane's k-th distance at B0 instead of +inf was measured too and changed
+// nothing, 0.688-0.692 against 0.690-0.692 ms per C3 call: not kept.)
+constexpr int kOrdBuckets = 256;  // counters per wave (a multiple of 64: four per lane)
+constexpr int kOrdShift = 19;     // bucket = float bits >> 19: 16 buckets per octave of the bound
+constexpr float kUbMargin = 1.0f + 0x1p-20f;
+
+// Buckets are logarithmic: the bits of a non-negative float order like its value, so bits >> 19
+// is monotone with 16 steps per octave, and the 256 buckets end at `top`, the step of the
+// wave's range (B0, or the largest finite bound when B0 is inf).  They reach 16 octaves below
+// it; whatever is lower, zero included, shares bucket 0, and whatever is above, +inf included,
+// the last.  Integer arithmetic only: a zero range (every reference equal to the query) or an
+// empty one cannot produce inf or NaN.  (Measured on the C3 micro-benchmark, DESIGN.md section
+// 4.5: 64 buckets linear in the bound were no faster than the sort they replace -- the first
+// tiles visited, far below B0, decide how fast the k-th distances fall, and they shared a bucket.)
+__device__ __forceinline__ int knn_bucket_top(float range) {
+  return static_cast<int>(__float_as_uint(range) >> kOrdShift);
+}
+__device__ __forceinline__ int knn_bucket(float lb, int top) {
+  const int below = top - static_cast<int>(__float_as_uint(lb) >> kOrdShift);
+  return max(0, kOrdBuckets - 1 - max(0, below));
+}
+
+// The wave's lower bound of a tile: hbox_lb2 against the wave's query box with the low 10 mantissa
+// bits cleared (room for the tile id beside it in one register of the scan; clearing them only
+// lowers a non-negative float, so it stays a lower bound and stays monotone).  The order, the drop
+// rule and the scan all use this one value.
+__device__ __forceinline__ float knn_tile_lb(const uint3& h, const float (&wl)[3], const float (&wh)[3]) {
+  return __uint_as_float(__float_as_uint(hbox_lb2(h, wl[0], wl[1], wl[2], wh[0], wh[1], wh[2])) & ~kTileIdBits);
+}
+
+// Upper bound of the computed d2 between a point in box [a_lo, a_hi] and a point of the half box
+// h (+inf when a corner of h is inf or NaN: fmaxf would drop a NaN side)
+__device__ __forceinline__ float hbox_ub2(const uint3& h, float alx, float aly, float alz, float ahx, float ahy,
+                                          float ahz) {
+  const float blx = half_lo(h.x), bly = half_hi(h.x), blz = half_lo(h.y);
+  const float bhx = half_hi(h.y), bhy = half_lo(h.z), bhz = half_hi(h.z);
+  const float fx = fmaxf(bhx - alx, ahx - blx), fy = fmaxf(bhy - aly, ahy - bly), fz = fmaxf(bhz - alz, ahz - blz);
+  const float u = ((fx * fx + fy * fy) + fz * fz) * kUbMargin;
+  const float s = ((fabsf(blx) + fabsf(bly)) + fabsf(blz)) + ((fabsf(bhx) + fabsf(bhy)) + fabsf(bhz));
+  return s < __builtin_huge_valf() ? u : __builtin_huge_valf();
+}
+
+// min over the wave of non-negative floats (+inf allowed): their bits order like the values
+__device__ __forceinline__ float wave_min_nonneg(float x) {
+  return __uint_as_float(~wave_umax_i(~__float_as_uint(x)));
+}
+
+// The wave's query box over its live lanes (wave-uniform: SGPRs); returns whether every live query
+// is finite.
+__device__ __forceinline__ bool knn_wave_box(bool live, float qx, float qy, float qz, float (&wl)[3], float (&wh)[3]) {
+  const float q[3] = {qx, qy, qz};
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    const float lo = live ? q[a] : __builtin_huge_valf(), hi = live ? q[a] : -__builtin_huge_valf();
+    wl[a] = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(-wave_max_nonneg_signed(-lo))));
+    wh[a] = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(wave_max_nonneg_signed(hi))));
+  }
+  return __ballot(live && !((fabsf(qx) + fabsf(qy)) + fabsf(qz) < __builtin_huge_valf())) == 0;
+}
+
+struct WaveOrder {
+  float b0;  // the certified bound (+inf: none)
+  int top;   // knn_bucket's
+  int kept;  // positions written to sordw
+};
+
+// Steps 1-2 for one wave.  hbox: the cloud's T half boxes (LDS); wl/wh: the wave's query box;
+// qfinite: every live query is finite; cnt: kOrdBuckets words of wave-private LDS; sordw: the
+// wave's kSordWords words, left holding `kept` tile ids in bucket order, three per word.
+// lbv[r] returns the lower bound of tile r * 64 + lane (the probe's output).
+template <int R>
+__device__ __forceinline__ WaveOrder knn_wave_order(const uint3* hbox, int T, int M, const float (&wl)[3],
+                                                    const float (&wh)[3], bool qfinite, uint32_t* cnt,
+                                                    uint32_t* sordw, float (&lbv)[R]) {
+  const int lane = threadIdx.x & 63;
+  const float inf = __builtin_huge_valf();
+  for (int i = lane; i < kSordWords; i += kWave) sordw[i] = 0u;
+  constexpr int kPer = kOrdBuckets / kWave;  // consecutive counters per lane
+#pragma unroll
+  for (int j = 0; j < kPer; ++j) cnt[j * kWave + lane] = 0u;
+  // this lane's tiles: lower bounds, the two smallest certified upper bounds, the largest bound
+  float m1 = inf, m2 = inf, lbmax = 0.0f;
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    lbv[r] = 0.0f;
+    if (r * 64 < T) {
+      const int t = r * 64 + lane;
+      if (t < T) {
+        const uint3 hb = hbox[t];
+        lbv[r] = knn_tile_lb(hb, wl, wh);
+        lbmax = fmaxf(lbmax, lbv[r] < inf ? lbv[r] : 0.0f);
+        // (the padded last tile holds fewer than kTile points: no certificate)
+        const float ub = (t + 1) * kTile <= M ? hbox_ub2(hb, wl[0], wl[1], wl[2], wh[0], wh[1], wh[2]) : inf;
+        const float u = ub >= 0.0f ? ub : inf;  // (NaN: an empty wave box)
+        m2 = fminf(m2, fmaxf(m1, u));
+        m1 = fminf(m1, u);
+      }
+    }
+  }
+  WaveOrder o;
+  {
+    const float g1 = wave_min_nonneg(m1);
+    const uint64_t own = __ballot(m1 == g1);
+    const int owner = own ? __builtin_ctzll(own) : 0;
+    const float g2 = wave_min_nonneg(lane == owner ? m2 : m1);
+    o.b0 = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(qfinite ? g2 : inf)));  // (SGPRs)
+  }
+  o.top = __builtin_amdgcn_readfirstlane(knn_bucket_top(o.b0 < inf ? o.b0 : wave_max_nonneg(lbmax)));
+  // pass 1: tiles per bucket
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+#pragma unroll
+  for (int r = 0; r < R; ++r)
+    if (r * 64 < T) {
+      const int t = r * 64 + lane;
+      if (t < T && !(lbv[r] > o.b0)) atomicAdd(&cnt[knn_bucket(lbv[r], o.top)], 1u);
+    }
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  // bucket bases: exclusive prefix sum over the wave (lane l owns counters l * kPer ..)
+  {
+    uint32_t c[kPer], sum = 0u;
+#pragma unroll
+    for (int j = 0; j < kPer; ++j) {
+      c[j] = cnt[lane * kPer + j];
+      sum += c[j];
+    }
+    uint32_t incl = sum;
+#pragma unroll
+    for (int off = 1; off < kWave; off <<= 1) {
+      const uint32_t up = static_cast<uint32_t>(__shfl_up(static_cast<int>(incl), off, kWave));
+      incl += lane >= off ? up : 0u;
+    }
+    o.kept = __builtin_amdgcn_readlane(static_cast<int>(incl), 63);
+    __builtin_amdgcn_wave_barrier();
+    uint32_t base = incl - sum;
+#pragma unroll
+    for (int j = 0; j < kPer; ++j) {
+      cnt[lane * kPer + j] = base;
+      base += c[j];
+    }
+  }
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  // pass 2: every kept tile takes a slot of its bucket
+#pragma unroll
+  for (int r = 0; r < R; ++r)
+    if (r * 64 < T) {
+      const int t = r * 64 + lane;
+      if (t < T && !(lbv[r] > o.b0)) {
+        const uint32_t p = atomicAdd(&cnt[knn_bucket(lbv[r], o.top)], 1u);
+        atomicOr(&sordw[p / 3], static_cast<uint32_t>(t) << (10 * (p % 3)));
+      }
+    }
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  return o;
+}
+
 // Every k in 17..32 selects the 32 nearest keys (the pruning bound is the 32nd) and writes the
 // first k: ordered by (d^2, index), the first k of the 32 nearest are the k nearest.  (Round 5
 // had a k < 32 instantiation bounding by the k-th key: its select loop over the slots cost 272 B
@@ -621,12 +796,11 @@ __global__ __launch_bounds__(kTiledThreads) __attribute__((amdgpu_waves_per_eu(3
     bx = slot % static_cast<int>(gridDim.x);
   }
   const int T = (M + kTile - 1) / kTile;
-  // 12 + 32 + 5.3 KB of LDS (half-precision boxes, candidate buffers, sorted tile order): three
+  // 12 + 32 + 5.3 KB of LDS (half-precision boxes, candidate buffers, tile order): three
   // workgroups per CU
   __shared__ uint3 hbox[kMaxTiles];
-  // each wave's tile order after the sort, three 10-bit tile ids per word (the chunked scan
-  // recomputes the keys from them): 16 key registers held across the scan spilled to scratch and
-  // were reloaded every chunk
+  // each wave's tile order, three 10-bit tile ids per word (the chunked scan recomputes the bounds
+  // from them: 16 registers of keys held across the scan spilled to scratch)
   __shared__ uint32_t sord[kTiledThreads / kWave][kSordWords];
   __shared__ double sbuf[kTiledThreads / kWave][kSelBufN][kWave];  // lane-private candidate buffers (packed keys)
   __shared__ float4 stile[kTiledThreads / kWave][kTile];            // the wave's current tile (appends)
@@ -650,27 +824,15 @@ __global__ __launch_bounds__(kTiledThreads) __attribute__((amdgpu_waves_per_eu(3
     const int sqn = sq0 + knn_fresh_lane();
     return __float_as_int(qsorted[static_cast<int64_t>(b) * Q + sqn].w);
   };
-  float wl[3] = {live ? qx : __builtin_huge_valf(), live ? qy : __builtin_huge_valf(),
-                 live ? qz : __builtin_huge_valf()};
-  float wh[3] = {live ? qx : -__builtin_huge_valf(), live ? qy : -__builtin_huge_valf(),
-                 live ? qz : -__builtin_huge_valf()};
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {  // (wave-uniform: SGPRs)
-    wl[a] = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(-wave_max_nonneg_signed(-wl[a]))));
-    wh[a] = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(wave_max_nonneg_signed(wh[a]))));
+  float wl[3], wh[3];
+  const bool qfinite = knn_wave_box(live, qx, qy, qz, wl, wh);
+  // the wave's tile order in sord[wave] (the counters alias the candidate buffer, empty until the
+  // scan starts)
+  WaveOrder ord;
+  {
+    float lbv[R];
+    ord = knn_wave_order<R>(hbox, T, M, wl, wh, qfinite, reinterpret_cast<uint32_t*>(sbuf[wave]), sord[wave], lbv);
   }
-  uint32_t keys[R];
-#pragma unroll
-  for (int r = 0; r < R; ++r) {
-    const int t = r * 64 + lane;
-    if (t < T) {
-      const float lb = hbox_lb2(hbox[t], wl[0], wl[1], wl[2], wh[0], wh[1], wh[2]);
-      keys[r] = (__float_as_uint(lb) & ~kTileIdBits) | static_cast<uint32_t>(t);
-    } else {
-      keys[r] = 0xFFFFFFFFu;
-    }
-  }
-  wave_bitonic<R>(keys);
 
   // This lane's 32 smallest keys so far, ascending.  A key (d2, index) is packed into the mantissa
   // of a double in [1, 2): bits 0x3FF0'0000'0000'0000 | d2_bits << 14 | index (M <= 16384: 14 index
@@ -741,7 +903,7 @@ __global__ __launch_bounds__(kTiledThreads) __attribute__((amdgpu_waves_per_eu(3
   // tiles some lane needs, found by a look-ahead test, was slower: 0.97 -> 1.11 ms per call,
   // profiles/round3/r3x_knn_diag_*.log.)
   const float* P = reinterpret_cast<const float*>(sorted) + static_cast<int64_t>(b) * T * kTile * 4;
-  // Visit the tile of sorted key `key` (its bound already known not to exceed wkth): the per-lane
+  // Visit tile `key` (its bound already known not to exceed wkth): the per-lane
   // test, then the distances, the filter and the appends.
   // (the tile's float for this lane, loaded by the caller once some lane is active)
   auto visit_loaded = [&](uint32_t key, float lbq, float v_cur) {
@@ -830,14 +992,13 @@ __global__ __launch_bounds__(kTiledThreads) __attribute__((amdgpu_waves_per_eu(3
     visit_loaded(key, lbq, v);
   };
 
-#if DVCP_KNN_CHUNK
-  // Chunked scan.  The sorted order is taken 64 positions at a time, one position per lane, and a
+  // Chunked scan.  The order is taken 64 positions at a time, one position per lane, and a
   // tile-parallel prefilter drops the positions no query can need: lane i tests its tile's box
   // against the boxes of the wave's kKnnSub lane groups (16 Hilbert-consecutive queries each) with
   // each group's largest k-th distance.  A position survives when some group's bound reaches its
   // k-th distance; only survivors get the per-lane test (visit).  The group bounds come from k-th
   // distances read at chunk start: merges only lower them, so a stale bound keeps a superset and
-  // the scan stays exact; the stop rule is re-checked at every surviving position.
+  // the scan stays exact; every surviving position is re-checked against the wave's current bound.
   constexpr int kKnnSub = 4, kSubLanes = kWave / kKnnSub;
   float gl[3] = {wl[0], wl[1], wl[2]}, gh[3] = {wh[0], wh[1], wh[2]};  // (overwritten below)
   {
@@ -865,44 +1026,36 @@ __global__ __launch_bounds__(kTiledThreads) __attribute__((amdgpu_waves_per_eu(3
     sgbox[wave][lane / kSubLanes][0] = make_float4(gl[0], gl[1], gl[2], 0.0f);
     sgbox[wave][lane / kSubLanes][1] = make_float4(gh[0], gh[1], gh[2], 0.0f);
   }
-  // the sorted order to LDS; the keys are recomputed per chunk from the tile id (the same
-  // expression as above: the same bits)
-#if DVCP_KNN_SORD
-  for (int i = lane; i < kSordWords; i += kWave) sord[wave][i] = 0u;
-  __builtin_amdgcn_wave_barrier();
-#pragma unroll
-  for (int r = 0; r < R; ++r) {
-    const int p = r * 64 + lane;
-    if (p < T) atomicOr(&sord[wave][p / 3], (keys[r] & kTileIdBits) << (10 * (p % 3)));
-  }
-  __builtin_amdgcn_wave_barrier();
-#endif
+  // The order (sord[wave], ord.kept positions) is in buckets of the wave's lower bound, not
+  // sorted inside one, so nothing here assumes a total order.  A position's bound is recomputed
+  // from its tile id (the same expression as in knn_wave_order: the same bits).  A position is
+  // needed iff its own bound does not exceed wkth; a bound above wkth at visit time skips that
+  // position only.  The scan ends after a chunk whose last position's bucket is above wkth's:
+  // every later tile has a bucket >= that one, and bucket(lb) > bucket(wkth) implies lb > wkth.
   bool stop = false;
 #pragma unroll 1
-  for (int base = 0; base < T && !stop; base += kWave) {
-    const bool inr = base + lane < T;
-#if DVCP_KNN_SORD
+  for (int base = 0; base < ord.kept && !stop; base += kWave) {
+    const bool inr = base + lane < ord.kept;
     const int pos = base + lane;
     const int tt = inr ? static_cast<int>((sord[wave][pos / 3] >> (10 * (pos % 3))) & kTileIdBits) : 0;
     const uint3 hb = hbox[tt];
-    const uint32_t mykey = inr ? (__float_as_uint(hbox_lb2(hb, wl[0], wl[1], wl[2], wh[0], wh[1], wh[2])) &
-                                  ~kTileIdBits) | static_cast<uint32_t>(tt)
-                               : 0xFFFFFFFFu;  // lane i: sorted position base + i
-#else
-    const uint32_t mykey = keys[base >> 6];
-    const int tt = inr ? static_cast<int>(mykey & kTileIdBits) : 0;
-    const uint3 hb = hbox[tt < T ? tt : 0];
-#endif
-    const float klb = __uint_as_float(mykey & ~kTileIdBits);
-    const uint64_t over = __ballot(!inr || klb > wkth);
-    const int lim = over ? __builtin_ctzll(over) : kWave;  // positions past lim are never needed
+    const float mylb = knn_tile_lb(hb, wl, wh);  // lane i: position base + i
+    const uint32_t mykey = __float_as_uint(mylb) | static_cast<uint32_t>(tt);
+    const int blast = __builtin_amdgcn_readlane(knn_bucket(mylb, ord.top), min(kWave, ord.kept - base) - 1);
     // the groups' k-th distances (largest per group) as of now
-    float gk = kth;
-#pragma unroll
-    for (int off = kSubLanes / 2; off > 0; off >>= 1) gk = fmaxf(gk, __shfl_xor(gk, off, kWave));
+    // (a row-wise DPP max of the non-negative bits, left in each group's last lane: no lane
+    // addresses to hold across the scan)
+    static_assert(kSubLanes == 16, "one DPP row per lane group");
+    uint32_t gk = __float_as_uint(kth);
+    gk = dpp_max_u<0x111, 0xF>(gk);
+    gk = dpp_max_u<0x112, 0xF>(gk);
+    gk = dpp_max_u<0x114, 0xF>(gk);
+    gk = dpp_max_u<0x118, 0xF>(gk);
     float gks[kKnnSub];
 #pragma unroll
-    for (int g = 0; g < kKnnSub; ++g) gks[g] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(gk), g * kSubLanes));
+    for (int g = 0; g < kKnnSub; ++g)
+      gks[g] = __uint_as_float(static_cast<uint32_t>(
+          __builtin_amdgcn_readlane(static_cast<int>(gk), g * kSubLanes + kSubLanes - 1)));
     const float blx = half_lo(hb.x), bly = half_hi(hb.x), blz = half_lo(hb.y);
     const float bhx = half_hi(hb.y), bhy = half_lo(hb.z), bhz = half_hi(hb.z);
     bool pass = false;
@@ -911,40 +1064,16 @@ __global__ __launch_bounds__(kTiledThreads) __attribute__((amdgpu_waves_per_eu(3
       const float4 lo = sgbox[wave][g][0], hi = sgbox[wave][g][1];
       pass |= box_box_lb2(lo.x, lo.y, lo.z, hi.x, hi.y, hi.z, blx, bly, blz, bhx, bhy, bhz) <= gks[g];
     }
-    uint64_t cand = __ballot(pass && inr) & (lim >= kWave ? ~0ull : ((1ull << lim) - 1ull));
-    if (lim < kWave) stop = true;
+    uint64_t cand = __ballot(pass && inr && !(mylb > wkth));
     while (cand) {
       const int i = __builtin_ctzll(cand);
       cand &= cand - 1ull;
       const uint32_t key = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(mykey), i));
-      if (__uint_as_float(key & ~kTileIdBits) > wkth) {  // every later tile is farther
-        stop = true;
-        break;
-      }
+      if (__uint_as_float(key & ~kTileIdBits) > wkth) continue;  // this tile only: a later one may be nearer
       visit(key);
     }
+    stop = blast > knn_bucket(wkth, ord.top);
   }
-#else
-  // one flat loop over the sorted tile order (not unrolled over the key registers: the merge is
-  // large, and the key register is a wave-uniform indexed read)
-  uint32_t key_next = T > 0 ? static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(keys[0]), 0)) : 0u;
-#pragma unroll 1
-  for (int pos = 0; pos < T; ++pos) {
-#ifdef DVCP_KNN_DIAG
-    {
-      const uint64_t now = __builtin_readcyclecounter();
-      if (dg_kind == 0) dg_skip_clk += now - dg_prev;
-      dg_prev = now;
-      dg_kind = 0;
-    }
-#endif
-    const uint32_t key = key_next;
-    if (pos + 1 < T)
-      key_next = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(keys[(pos + 1) >> 6]), (pos + 1) & 63));
-    if (__uint_as_float(key & ~kTileIdBits) > wkth) break;  // every later tile is farther
-    visit(key);
-  }
-#endif
   merge();
 #ifdef DVCP_KNN_DIAG
   const uint64_t dg_total = __builtin_readcyclecounter() - dg_t0;
@@ -1049,6 +1178,60 @@ __global__ __launch_bounds__(kTiledThreads) __attribute__((amdgpu_waves_per_eu(3
   }
 }
 
+// Test hook (dvcp_knn_tiled_order_probe): knn_sel_query_kernel's wave box and tile order for every
+// wave, written out instead of scanned.  Row = cloud * ceil(Q / 64) + wave of the curve order.
+template <int R>
+__global__ __launch_bounds__(kTiledThreads) void knn_order_probe_kernel(const float4* __restrict__ tbox,
+                                                                        const float4* __restrict__ qsorted, int M,
+                                                                        int Q, int32_t* __restrict__ info,
+                                                                        int32_t* __restrict__ order,
+                                                                        float* __restrict__ lbs,
+                                                                        int32_t* __restrict__ buckets, int B8) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int b = blockIdx.y, bx = blockIdx.x;
+  if ((B8 & 1) != 0) {  // XCD-aware cloud mapping, as knn_sel_query_kernel
+    const int lin = static_cast<int>(blockIdx.y * gridDim.x + blockIdx.x);
+    const int xo = lin & 7, slot = lin >> 3;
+    b = xo + 8 * (slot / static_cast<int>(gridDim.x));
+    bx = slot % static_cast<int>(gridDim.x);
+  }
+  const int T = (M + kTile - 1) / kTile;
+  __shared__ uint3 hbox[kMaxTiles];
+  __shared__ uint32_t sord[kTiledThreads / kWave][kSordWords];
+  __shared__ uint32_t scnt[kTiledThreads / kWave][kOrdBuckets];
+  {
+    const float4* tbg = tbox + static_cast<int64_t>(b) * T * 2;
+    for (int i = threadIdx.x; i < T; i += kTiledThreads) hbox[i] = pack_hbox(tbg[2 * i], tbg[2 * i + 1]);
+    __syncthreads();
+  }
+  const int sq0 = __builtin_amdgcn_readfirstlane((bx * (kTiledThreads / kWave) + wave) * kWave);
+  const int sq = sq0 + lane;
+  if (sq0 >= Q) return;
+  const bool live = sq < Q;
+  const float4 qrow = live ? qsorted[static_cast<int64_t>(b) * Q + sq] : make_float4(0.f, 0.f, 0.f, 0.f);
+  float wl[3], wh[3];
+  const bool qfinite = knn_wave_box(live, qrow.x, qrow.y, qrow.z, wl, wh);
+  float lbv[R];
+  const WaveOrder ord = knn_wave_order<R>(hbox, T, M, wl, wh, qfinite, scnt[wave], sord[wave], lbv);
+  const int64_t row = static_cast<int64_t>(b) * ((Q + kWave - 1) / kWave) + sq0 / kWave;
+  if (lane == 0) {
+    info[row * 4 + 0] = T - ord.kept;
+    info[row * 4 + 1] = ord.kept;
+    info[row * 4 + 2] = ord.b0 < __builtin_huge_valf() ? 1 : 0;
+    info[row * 4 + 3] = __float_as_int(ord.b0);
+  }
+  for (int p = lane; p < T; p += kWave)
+    order[row * T + p] = p < ord.kept ? static_cast<int>((sord[wave][p / 3] >> (10 * (p % 3))) & kTileIdBits) : -1;
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    const int t = r * 64 + lane;
+    if (t < T) {
+      lbs[row * T + t] = lbv[r];
+      buckets[row * T + t] = lbv[r] > ord.b0 ? -1 : knn_bucket(lbv[r], ord.top);
+    }
+  }
+}
+
 }  // namespace dvcp
 
 extern "C" int64_t dvcp_knn_tiled_workspace_bytes(int B, int M, int Q) {
@@ -1058,16 +1241,10 @@ extern "C" int64_t dvcp_knn_tiled_workspace_bytes(int B, int M, int Q) {
          dvcp::align256(16 * int64_t(B) * Q) + dvcp::align256(dvcp::tiled_zeroed_bytes(B));
 }
 
-static int knn_tiled_impl(int dtype, const void* ref, int64_t rb, int64_t rc, int64_t rn, int M, const void* qry,
-                          int64_t qb, int64_t qc, int64_t qn, int Q, int B, int k, void* workspace, float* dist,
-                          int32_t* idx, int64_t* idx64, void* stream, bool insertion) {
-  DVCP_REQUIRE(ref && qry && workspace, "dvcp_knn_tiled: null pointer");
-  DVCP_REQUIRE(k > 0 && k <= 32 && M >= 0 && Q >= 0 && B >= 0 && B <= 65535, "dvcp_knn_tiled: bad sizes");
-  DVCP_REQUIRE(M <= dvcp::kMaxTiles * dvcp::kTile, "dvcp_knn_tiled: M=%d > %d", M, dvcp::kMaxTiles * dvcp::kTile);
-  DVCP_REQUIRE(dtype == DVCP_F32 || dtype == DVCP_F64, "dvcp_knn_tiled: bad dtype %d", dtype);
-  if (B == 0 || Q == 0) return DVCP_OK;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const dvcp::TiledLayout L = dvcp::tiled_layout(workspace, B, M, Q);
+// The reference tiles and the queries' curve order into the workspace (every caller's first step).
+static int knn_tiled_build(int dtype, const void* ref, int64_t rb, int64_t rc, int64_t rn, int M, const void* qry,
+                           int64_t qb, int64_t qc, int64_t qn, int Q, int B, const dvcp::TiledLayout& L,
+                           hipStream_t st) {
   // queries: bounding box, cell counts, scan, then the scatter beside the reference build
   if (hipMemsetAsync(L.qbins, 0, dvcp::tiled_zeroed_bytes(B), st) != hipSuccess) {
     dvcp::set_error("dvcp_knn_tiled: memset failed");
@@ -1091,7 +1268,20 @@ static int knn_tiled_impl(int dtype, const void* ref, int64_t rb, int64_t rc, in
     hipLaunchKernelGGL((dvcp::knn_tiled_build_kernel<double>), bgrid, dim3(dvcp::kBuildThreads), 0, st,
                        dvcp::PointsView<double>{static_cast<const double*>(ref), rb, rc, rn}, M, qv, Q, L);
   }
-  if (int e = dvcp::launch_status("dvcp_knn_tiled(build)")) return e;
+  return dvcp::launch_status("dvcp_knn_tiled(build)");
+}
+
+static int knn_tiled_impl(int dtype, const void* ref, int64_t rb, int64_t rc, int64_t rn, int M, const void* qry,
+                          int64_t qb, int64_t qc, int64_t qn, int Q, int B, int k, void* workspace, float* dist,
+                          int32_t* idx, int64_t* idx64, void* stream, bool insertion) {
+  DVCP_REQUIRE(ref && qry && workspace, "dvcp_knn_tiled: null pointer");
+  DVCP_REQUIRE(k > 0 && k <= 32 && M >= 0 && Q >= 0 && B >= 0 && B <= 65535, "dvcp_knn_tiled: bad sizes");
+  DVCP_REQUIRE(M <= dvcp::kMaxTiles * dvcp::kTile, "dvcp_knn_tiled: M=%d > %d", M, dvcp::kMaxTiles * dvcp::kTile);
+  DVCP_REQUIRE(dtype == DVCP_F32 || dtype == DVCP_F64, "dvcp_knn_tiled: bad dtype %d", dtype);
+  if (B == 0 || Q == 0) return DVCP_OK;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const dvcp::TiledLayout L = dvcp::tiled_layout(workspace, B, M, Q);
+  if (int e = knn_tiled_build(dtype, ref, rb, rc, rn, M, qry, qb, qc, qn, Q, B, L, st)) return e;
   const int T = dvcp::ceil_div(M, dvcp::kTile);
   dim3 grid(dvcp::ceil_div(Q, dvcp::kTiledThreads), B);
   const int xcd = B % 8 == 0 ? 1 : 0;  // XCD-aware cloud mapping (equal clouds per XCD)
@@ -1143,4 +1333,37 @@ extern "C" int dvcp_knn_tiled_insert(int dtype, const void* ref, int64_t rb, int
                                      const void* qry, int64_t qb, int64_t qc, int64_t qn, int Q, int B, int k,
                                      void* workspace, float* dist, int32_t* idx, int64_t* idx64, void* stream) {
   return knn_tiled_impl(dtype, ref, rb, rc, rn, M, qry, qb, qc, qn, Q, B, k, workspace, dist, idx, idx64, stream, true);
+}
+
+// Test hook: the wave box, certified bound and tile order that dvcp_knn_tiled's k = 17..32 kernel
+// computes for every wave of 64 curve-ordered queries (see include/dvcp.h).
+extern "C" int dvcp_knn_tiled_order_probe(int dtype, const void* ref, int64_t rb, int64_t rc, int64_t rn, int M,
+                                          const void* qry, int64_t qb, int64_t qc, int64_t qn, int Q, int B,
+                                          void* workspace, int32_t* info, int32_t* order, float* lb,
+                                          int32_t* bucket, void* stream) {
+  DVCP_REQUIRE(ref && qry && workspace && info && order && lb && bucket, "dvcp_knn_tiled_order_probe: null pointer");
+  DVCP_REQUIRE(M > 0 && Q > 0 && B > 0 && B <= 65535, "dvcp_knn_tiled_order_probe: bad sizes");
+  DVCP_REQUIRE(M <= dvcp::kMaxTiles * dvcp::kTile, "dvcp_knn_tiled_order_probe: M=%d > %d", M,
+               dvcp::kMaxTiles * dvcp::kTile);
+  DVCP_REQUIRE(dtype == DVCP_F32 || dtype == DVCP_F64, "dvcp_knn_tiled_order_probe: bad dtype %d", dtype);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const dvcp::TiledLayout L = dvcp::tiled_layout(workspace, B, M, Q);
+  if (int e = knn_tiled_build(dtype, ref, rb, rc, rn, M, qry, qb, qc, qn, Q, B, L, st)) return e;
+  const int T = dvcp::ceil_div(M, dvcp::kTile);
+  const dim3 grid(dvcp::ceil_div(Q, dvcp::kTiledThreads), B);
+  const int xcd = B % 8 == 0 ? 1 : 0;
+#define DVCP_KNNP(RR)                                                                                            \
+  if (T <= 64 * RR) {                                                                                            \
+    hipLaunchKernelGGL((dvcp::knn_order_probe_kernel<RR>), grid, dim3(dvcp::kTiledThreads), 0, st, L.tbox,        \
+                       L.qsorted, M, Q, info, order, lb, bucket, xcd);                                            \
+    return dvcp::launch_status("dvcp_knn_tiled_order_probe");                                                    \
+  }
+  DVCP_KNNP(1)
+  DVCP_KNNP(2)
+  DVCP_KNNP(4)
+  DVCP_KNNP(8)
+  DVCP_KNNP(16)
+#undef DVCP_KNNP
+  dvcp::set_error("dvcp_knn_tiled_order_probe: unsupported M=%d", M);
+  return DVCP_EINVAL;
 }

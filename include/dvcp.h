@@ -242,8 +242,9 @@ int64_t dvcp_knn_grid_workspace_bytes(int B, int M);
 /* Exact kNN over spatially sorted reference tiles: same contract and results as dvcp_knn
  * (replaces knn_cuda.KNN at get_cat_feat_tgt.py:45,52).  References are Morton-sorted into
  * 16-point tiles with boxes and queries into Morton order; each wave of 64 queries scans tiles in
- * ascending lower-bound order and stops once no unscanned tile can hold a point at or below any
- * lane's k-th distance.  For k > 16 each lane buffers its candidates in LDS and the wave merges
+ * ascending lower-bound order (k > 16: in buckets of it, behind a certified upper bound of the
+ * 32nd distance) and stops once no unscanned tile can hold a point at or below any lane's k-th
+ * distance.  For k > 16 each lane buffers its candidates in LDS and the wave merges
  * them into the sorted lists with bitonic networks.  M <= 16384, k <= 32.
  * workspace: dvcp_knn_tiled_workspace_bytes(B, M, Q) bytes of device memory. */
 int dvcp_knn_tiled(int dtype, const void* ref, int64_t rb, int64_t rc, int64_t rn, int M,
@@ -255,6 +256,19 @@ int dvcp_knn_tiled_insert(int dtype, const void* ref, int64_t rb, int64_t rc, in
                           const void* qry, int64_t qb, int64_t qc, int64_t qn, int Q, int B, int k,
                           void* workspace, float* dist, int32_t* idx, int64_t* idx64, void* stream);
 int64_t dvcp_knn_tiled_workspace_bytes(int B, int M, int Q);
+/* Test hook: the tile order that dvcp_knn_tiled's k = 17..32 kernel gives every wave of 64
+ * curve-ordered queries (the same device code, written out instead of scanned).  With T = ceil(M / 16)
+ * tiles and W = ceil(Q / 64) waves per cloud, row = cloud * W + wave:
+ *   info   B*W x 4 int32: tiles dropped (lower bound above the certified bound B0), positions kept,
+ *                         1 if B0 is finite, the bits of B0;
+ *   order  B*W x T int32: the kept tile ids in visiting order, then -1;
+ *   lb     B*W x T fp32:  the wave's lower bound of every tile, by tile id;
+ *   bucket B*W x T int32: the tile's bucket (non-decreasing along order), -1 if dropped.
+ * workspace as dvcp_knn_tiled; M, Q, B > 0, M <= 16384. */
+int dvcp_knn_tiled_order_probe(int dtype, const void* ref, int64_t rb, int64_t rc, int64_t rn, int M,
+                               const void* qry, int64_t qb, int64_t qc, int64_t qn, int Q, int B,
+                               void* workspace, int32_t* info, int32_t* order, float* lb,
+                               int32_t* bucket, void* stream);
 
 /* Deep feature embedding on a materialised input.  Replaces deep_feat_embedding.py:23-61
  * (X.float(); Linear 35-32-32-32, no activations; MaxPool1d(32) over the neighbour axis).
