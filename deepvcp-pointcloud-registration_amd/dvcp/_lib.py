@@ -17,7 +17,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DVCP_LIB_PATH") or os.path.join(_HERE, "libdvcp_hip.so")
 
 F32, F64 = 0, 1
-ABI_VERSION = 4   # include/dvcp.h DVCP_ABI_VERSION
+ABI_VERSION = 5   # include/dvcp.h DVCP_ABI_VERSION
 _P = ctypes.c_void_p
 _I = ctypes.c_int
 _L = ctypes.c_int64
@@ -47,7 +47,6 @@ SIGNATURES = {
     "dvcp_src_keypoints": [_I, _P, _P, _I, _P, _I, _I, _P, _D, _I, _P, _L, _P, _P, _P, _P],
     "dvcp_voxelize": [_I, _P, _L, _L, _L, _I, _I, _D, _D, _I, _P, _P, _P],
     "dvcp_knn": [_I, _P, _L, _L, _L, _I, _P, _L, _L, _L, _I, _I, _I, _P, _P, _P, _P],
-    "dvcp_knn_grid": [_I, _P, _L, _L, _L, _I, _P, _L, _L, _L, _I, _I, _I, _P, _P, _P, _P, _P],
     "dvcp_knn_tiled": [_I, _P, _L, _L, _L, _I, _P, _L, _L, _L, _I, _I, _I, _P, _P, _P, _P, _P],
     "dvcp_knn_tiled_insert": [_I, _P, _L, _L, _L, _I, _P, _L, _L, _L, _I, _I, _I, _P, _P, _P, _P, _P],
     "dvcp_knn_tiled_order_probe": [_I, _P, _L, _L, _L, _I, _P, _L, _L, _L, _I, _I, _P, _P, _P, _P, _P, _P],
@@ -107,8 +106,6 @@ def load():
     if lib.dvcp_abi_version() != ABI_VERSION:
         raise RuntimeError(f"dvcp: {LIB_PATH} has ABI version {lib.dvcp_abi_version()}, this package expects "
                            f"{ABI_VERSION}: rebuild it (make -j16 in deepvcp-pointcloud-registration_amd/)")
-    lib.dvcp_knn_grid_workspace_bytes.restype = ctypes.c_int64
-    lib.dvcp_knn_grid_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int]
     lib.dvcp_knn_tiled_workspace_bytes.restype = ctypes.c_int64
     lib.dvcp_knn_tiled_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
     lib.dvcp_fps_workspace_bytes.restype = ctypes.c_int64
@@ -160,7 +157,7 @@ def load():
 
 
 def exported_symbols():
-    return ["dvcp_last_error", "dvcp_abi_version", "dvcp_knn_grid_workspace_bytes",
+    return ["dvcp_last_error", "dvcp_abi_version",
             "dvcp_knn_tiled_workspace_bytes", "dvcp_ball_query_workspace_bytes",
             "dvcp_sa_group_mlp_workspace_bytes", "dvcp_dfe_backward_workspace_bytes",
             "dvcp_dfe_tgt_backward_workspace_bytes",

@@ -348,9 +348,9 @@ def voxelize(pts, r, s, G, pdim=1):
 #   tiled_insert: the same scan inserting every candidate into the sorted list at once (the
 #          round-2 kernel, dvcp_knn_tiled_insert), kept for parity tests and A/B timing.
 #   brute: index-order scan of every reference point (dvcp_knn); best for small M.
-#   grid:  per-query cell-shell search (dvcp_knn_grid); loses on the forward's workload, where
-#          most voxel candidates lie outside the target cloud (profiles/round1: 35.8 ms vs 12.4 ms
-#          brute per C3 step).  Kept as an option.
+# (A per-query cell-shell search over a uniform grid left the tree with ABI version 5: it lost on
+# the forward's workload, where most voxel candidates lie outside the target cloud --
+# profiles/round1: 35.8 ms vs 12.4 ms brute per C3 step.)
 KNN_TILED_MIN_M = 512
 KNN_TILED_MAX_M = 16384
 
@@ -375,15 +375,13 @@ def knn(ref, qry, k, ref_pdim=1, qry_pdim=1, want_idx64=True, method=None):
     method = method or knn_method(M)
     if method in ("tiled", "tiled_insert"):
         ws = torch.empty(int(_lib.load().dvcp_knn_tiled_workspace_bytes(B, M, Q)), dtype=torch.uint8, device=dev)
-        call("dvcp_knn_tiled" if method == "tiled" else "dvcp_knn_tiled_insert", dtype_code(ref), ptr(ref), rb, rc, rn, M, ptr(qry), qb, qc, qn, Q, B, int(k), ptr(ws),
+        call("dvcp_knn_" + method, dtype_code(ref), ptr(ref), rb, rc, rn, M, ptr(qry), qb, qc, qn, Q, B, int(k), ptr(ws),
              ptr(dist), ptr(idx), ptr(idx64), stream(), work=work)
-    elif method == "grid":
-        ws = torch.empty(int(_lib.load().dvcp_knn_grid_workspace_bytes(B, M)), dtype=torch.uint8, device=dev)
-        call("dvcp_knn_grid", dtype_code(ref), ptr(ref), rb, rc, rn, M, ptr(qry), qb, qc, qn, Q, B, int(k), ptr(ws),
-             ptr(dist), ptr(idx), ptr(idx64), stream(), work=work)
-    else:
+    elif method == "brute":
         call("dvcp_knn", dtype_code(ref), ptr(ref), rb, rc, rn, M, ptr(qry), qb, qc, qn, Q, B, int(k), ptr(dist),
              ptr(idx), ptr(idx64), stream(), work=work)
+    else:
+        raise ValueError(f"dvcp: unknown kNN method {method!r} (tiled, tiled_insert or brute)")
     return dist, idx, idx64
 
 

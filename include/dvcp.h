@@ -35,7 +35,7 @@ extern "C" {
 #define DVCP_EHIP (-2)      /* HIP launch error */
 
 /* Bumped on every incompatible signature change; dvcp/_lib.py refuses a library whose version differs. */
-#define DVCP_ABI_VERSION 4
+#define DVCP_ABI_VERSION 5
 
 const char* dvcp_last_error(void);
 int dvcp_abi_version(void);
@@ -229,15 +229,6 @@ int dvcp_voxelize(int dtype, const void* pts, int64_t pb, int64_t pc, int64_t pn
 int dvcp_knn(int dtype, const void* ref, int64_t rb, int64_t rc, int64_t rn, int M,
              const void* qry, int64_t qb, int64_t qc, int64_t qn, int Q, int B, int k,
              float* dist, int32_t* idx, int64_t* idx64, void* stream);
-
-/* Exact kNN through a uniform cell grid (same contract and outputs as dvcp_knn).  The reference
- * set is counting-sorted into cells once per cloud, then each query scans Chebyshev shells of
- * cells around its home cell until no unscanned cell can hold a point at or below its k-th
- * distance.  workspace: dvcp_knn_grid_workspace_bytes(B, M) bytes of device memory. */
-int dvcp_knn_grid(int dtype, const void* ref, int64_t rb, int64_t rc, int64_t rn, int M,
-                  const void* qry, int64_t qb, int64_t qc, int64_t qn, int Q, int B, int k,
-                  void* workspace, float* dist, int32_t* idx, int64_t* idx64, void* stream);
-int64_t dvcp_knn_grid_workspace_bytes(int B, int M);
 
 /* Exact kNN over spatially sorted reference tiles: same contract and results as dvcp_knn
  * (replaces knn_cuda.KNN at get_cat_feat_tgt.py:45,52).  References are Morton-sorted into

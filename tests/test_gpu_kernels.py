@@ -529,7 +529,7 @@ def test_knn_golden(cuda, name):
     assert torch.equal(d.cpu(), T(z["dist"]))
 
 
-@pytest.mark.parametrize("method", ["tiled", "tiled_insert", "brute", "grid"])
+@pytest.mark.parametrize("method", ["tiled", "tiled_insert", "brute"])
 @pytest.mark.parametrize("name", ["knn_f32", "knn_dyadic"])
 def test_knn_methods_golden(cuda, name, method):
     """Every kNN method on the golden fixtures (forced regardless of M)."""
@@ -553,7 +553,7 @@ def _c3_knn_inputs(cuda, M=10000, Q=20000, B=2, seed=113):
     return ref.to(cuda), qry.to(cuda)
 
 
-@pytest.mark.parametrize("method", ["tiled", "tiled_insert", "grid"])
+@pytest.mark.parametrize("method", ["tiled", "tiled_insert"])
 @pytest.mark.parametrize("k", [1, 5, 20, 32])
 def test_knn_method_equals_brute_full_size(cuda, k, method):
     from dvcp import ops
@@ -575,6 +575,35 @@ def test_knn_tiled_edges_equal_brute(cuda, M, Q, k):
     d2, i2, i64 = ops.knn(ref, qry, k, method="tiled")
     assert torch.equal(i1, i2) and torch.equal(d1, d2)
     assert torch.equal(i64, i2.long())
+
+
+@pytest.mark.parametrize("k", [1, 8, 9, 16, 17, 32])
+@pytest.mark.parametrize("M", [1024, 1025, 2048, 2049, 4096, 4097, 8192, 8193])
+def test_knn_tiled_dispatch_boundaries(cuda, M, k):
+    """Each edge of dvcp_knn_tiled's dispatch against the brute-force kernel, bit for bit.  By tile
+    count T = ceil(M / 16): 64 | 65, 128 | 129, 256 | 257, 512 | 513, where the selection kernel and
+    the order probe change their registers of tile bounds (1, 2, 4, 8, 16), the insertion kernel
+    its registers of tile keys (k <= 8: 1 | 16 at T = 64 | 65; 32 slots: 1, 2, 4, 8, 16).  By k:
+    1 | 8 | 16 slots of the insertion kernel (1, 8 and 9, 16), then the selection kernel, or 32
+    slots under tiled_insert (17, 32).  Q = 130 leaves a ragged last wave; M >= 5100 includes the
+    duplicated points (ties)."""
+    from dvcp import ops
+    ref, qry = _c3_knn_inputs(cuda, M=M, Q=130, B=2, seed=400 + M)
+    d1, i1, j1 = ops.knn(ref, qry, k, method="brute")
+    for method in ("tiled", "tiled_insert"):
+        d2, i2, j2 = ops.knn(ref, qry, k, method=method)
+        assert torch.equal(d1, d2), (M, k, method)
+        assert torch.equal(i1, i2) and i2.dtype == torch.int32, (M, k, method)
+        assert torch.equal(j1, j2) and j2.dtype == torch.int64, (M, k, method)
+
+
+def test_knn_unknown_method_raises(cuda):
+    """A method string ops.knn does not know is an error, not the brute-force kernel."""
+    from dvcp import ops
+    ref, qry = _c3_knn_inputs(cuda, M=600, Q=70, B=1)
+    for method in ("grid", "Tiled"):
+        with pytest.raises(ValueError):
+            ops.knn(ref, qry, 4, method=method)
 
 
 @pytest.mark.parametrize("B", [8, 16])

@@ -12,7 +12,7 @@ HIPFLAGS="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -mcode-object-version=5 -ff
   -fhip-fp32-correctly-rounded-divide-sqrt -Wall -Wno-unused-function -I../include"
 case $stem in
   fps) EXTRA="-mllvm -amdgpu-promote-alloca-to-vector-limit=2048 -fno-slp-vectorize" ;;
-  knn_tiled) EXTRA="-mllvm -amdgpu-promote-alloca-to-vector-limit=2048" ;;
+  knn_tiled|knn_tiled_*) EXTRA="-mllvm -amdgpu-promote-alloca-to-vector-limit=2048" ;;
   sa_bn) EXTRA="-mllvm -amdgpu-promote-alloca-to-vector-limit=4096" ;;
   *) EXTRA="" ;;
 esac
