@@ -20,7 +20,7 @@ namespace dvcp {
 
 
 // DVCP_CPG_SPLIT3 (default): conv1 on the bf16 matrix cores (v_mfma_f32_16x16x32_bf16) with the
-// fp32-accurate three-way split of sa_mlp_mfma.hip: each 8-channel quarter of the cost volume is
+// fp32-accurate three-way split of sa_mfma_common.h: each 8-channel quarter of the cost volume is
 // stored in LDS as three bf16 piece images ([piece][cell][8 channels], 16 B per cell and piece,
 // split once when the volume is built) and each quarter's weights as three B-fragment images; a
 // k-step covers 4 taps x 8 channels (K = 32), 7 k-steps per quarter (taps 0..26 + one zero tap),

@@ -13,7 +13,7 @@
 //                        -> rows in registers, output channels on lanes
 // so the max over rows is a per-lane max over registers plus one exchange between lane halves.
 // Input channel order of layer 1's k-step s: lane half 0 takes [dx, dy, dz, f0 .. f15], half 1
-// [0, 0, 0, f16 .. f31] (19 k-steps; see sa_mlp_mfma.hip).
+// [0, 0, 0, f16 .. f31] (19 k-steps; see sa_mfma_plain.hip).
 // Everything before the GEMMs is the reference's arithmetic as in dfe_tgt_kernel (dfe.hip):
 // dist_sum in fp64 summed in neighbour order, w = dist / dist_sum in fp64, feature x w in fp64
 // rounded to fp32, coordinates differenced in the point dtype.  The MFMA is a k-ordered fp32 fma
@@ -75,7 +75,7 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 // without packed fp32 (target attribute) ran 11x slower with wrong results: not a usable switch.)
 
 // x = x0 + x1 + x2 exactly in three bf16 pieces; a.b from the six significant piece products
-// (the fp32-accurate split of sa_mlp_mfma.hip, whose header gives the error bound)
+// (the fp32-accurate split of sa_mfma_common.h, whose header gives the error bound)
 struct DfeSplit3 {
   bf16x8 p0, p1, p2;
 };

@@ -27,7 +27,7 @@
 // a product over entries (the weight gradients).  So z1 is formed in both (two fp32 MFMA k-steps
 // from U each); z2 in N for the statistics, the forward max and dW2, in T for the backward chain
 // gz2 -> gh1 = gz2 W2 (N) -> gz1 (N) -> dW1 = gz1^T [x].  Products over 16+ channels run as the
-// three-way bf16 split of sa_mlp_mfma.hip (six v_mfma_f32_32x32x16_bf16, fp32-accurate).
+// three-way bf16 split of sa_mfma_common.h (six v_mfma_f32_32x32x16_bf16, fp32-accurate).
 //
 // Statistics are summed per entry in fp64 (z^2 exact): the variance is E[z^2] - E[z]^2, a
 // difference of nearly equal sums wherever |mean| >> std (sa1's first layer sees local

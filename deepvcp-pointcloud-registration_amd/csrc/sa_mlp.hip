@@ -3,17 +3,21 @@
 // Reference: gather (B, S, nsample, 3+D) (local xyz, features), [Conv2d 1x1 -> BN2d -> ReLU]
 // per layer in fp32, then max over nsample.  The padded slots of query_ball_point repeat the
 // first hit (:104-106), and a row's MLP output depends only on that row, so the max over the
-// distinct hits is bit-identical to the max over all nsample slots.  This kernel therefore
+// distinct hits is bit-identical to the max over all nsample slots.  Every kernel therefore
 // runs the MLP on the distinct hits only (count/list from dvcp_ball_query): at sa1
 // (r = 0.1, ~9 hits of 256 slots) that is ~28x fewer rows than the reference evaluates.
 //
-// Layout: one workgroup = `cpb` consecutive centres of one cloud; their hit rows are packed
+// This file holds the dispatch and the row-per-thread kernel, which serves the two-layer tables
+// that the matrix-core kernels (sa_mfma_*.hip) do not take: the paper's 32-32 table, and sa2 / sa3
+// with channel-first or fp64 features.  The three-layer sa1 tables run on sa1_mfma_kernel only.
+//
+// Layout of the row-per-thread kernel: one workgroup = `cpb` consecutive centres of one cloud; their hit rows are packed
 // back to back (prefix sum in LDS) and processed 256 rows per pass, one row per thread, with
 // the layer weights read as wave-uniform scalar loads (SGPR operands) and activations in VGPRs.
 // The max over a centre's rows is an LDS atomic max on the fp32 bit pattern (outputs are
 // post-ReLU, hence >= +0, so unsigned order is float order).
 
-#include "common.h"
+#include "sa_mfma_common.h"
 
 namespace dvcp {
 
@@ -44,14 +48,14 @@ __device__ __forceinline__ void sa_layer(const float (&x)[CIN], float (&y)[COUT]
   }
 }
 
-template <typename T, typename FT, int D, int C1, int C2, int C3>
+template <typename T, typename FT, int D, int C1, int C2>
 __global__ __launch_bounds__(kSaThreads) void sa_mlp_kernel(PointsView<T> pts, PointsView<T> ctr, int S,
                                                             FeatView<FT> feat, const int32_t* __restrict__ count,
                                                             const int32_t* __restrict__ list, int nsample, int cpb,
                                                             const float* __restrict__ params,
                                                             float* __restrict__ out) {
   constexpr int C0 = 3 + D;
-  constexpr int CL = C3 > 0 ? C3 : C2;
+  constexpr int CL = C2;
   __shared__ int pref[kSaMaxCpb + 1];
   __shared__ uint32_t mx[kSaMaxCpb * CL];
 
@@ -61,7 +65,6 @@ __global__ __launch_bounds__(kSaThreads) void sa_mlp_kernel(PointsView<T> pts, P
   const int tid = threadIdx.x;
 
   const float* p2 = params + C0 * C1 + 3 * C1;
-  const float* p3 = p2 + C1 * C2 + 3 * C2;
   for (int i = tid; i < nc * CL; i += kSaThreads) mx[i] = 0u;
 
   if (tid < 64) {  // inclusive scan of the hit counts of this block's centres (nc <= 64)
@@ -103,15 +106,8 @@ __global__ __launch_bounds__(kSaThreads) void sa_mlp_kernel(PointsView<T> pts, P
       float y2[C2];
       sa_layer<C1, C2>(y1, y2, p2);
       uint32_t* m = mx + ci * CL;
-      if constexpr (C3 > 0) {
-        float y3[C3];
-        sa_layer<C2, C3>(y2, y3, p3);
 #pragma unroll
-        for (int co = 0; co < C3; ++co) atomicMax(m + co, __float_as_uint(y3[co]));
-      } else {
-#pragma unroll
-        for (int co = 0; co < C2; ++co) atomicMax(m + co, __float_as_uint(y2[co]));
-      }
+      for (int co = 0; co < C2; ++co) atomicMax(m + co, __float_as_uint(y2[co]));
     }
   }
   __syncthreads();
@@ -121,37 +117,40 @@ __global__ __launch_bounds__(kSaThreads) void sa_mlp_kernel(PointsView<T> pts, P
   }
 }
 
-// fp32 MFMA path for the two-layer tables (sa_mlp_mfma.hip)
+// The two-layer tables on the matrix cores (sa_mfma_*.hip): with a workspace the centres' order,
+// the per-point pre-pass and the table's pipelined kernel; without one the plain kernel.
 template <typename T, int D, int C1, int C2>
-int launch_sa_mfma(const void* xyz, int64_t sb, int64_t sc, int64_t sn, int N, const void* c, int64_t cb, int64_t cc,
-                   int64_t cn, int S, int B, const float* feat, int64_t fb, int64_t fn, const int32_t* count,
-                   const int32_t* list, int nsample, const float* params, float* U, int32_t* order, float* out,
-                   const int64_t* rows, int Nf, hipStream_t st);
+static int launch_sa_mfma(const void* xyz, int64_t sb, int64_t sc, int64_t sn, int N, const void* c, int64_t cb,
+                          int64_t cc, int64_t cn, int S, int B, const float* feat, int64_t fb, int64_t fn,
+                          const int32_t* count, const int32_t* list, int nsample, const float* params, float* U,
+                          int32_t* order, float* out, const int64_t* frows, int Nf, hipStream_t st) {
+  const SaTableArgs<T> a{PointsView<T>{static_cast<const T*>(xyz), sb, sc, sn},
+                         PointsView<T>{static_cast<const T*>(c), cb, cc, cn},
+                         S, B, feat, fb, fn, count, list, nsample, params, U, static_cast<int64_t>(N) * C1, order, out};
+  if (order) launch_sa_order<T>(a.ctr, S, B, order, st);
+  if (U) {
+    launch_sa_pre<D, C1>(feat, fb, fn, N, B, params, U, frows, Nf, st);
+    if constexpr (D == 32)
+      launch_sa2_mfma<T>(a, st);
+    else
+      launch_sa3_mfma<T>(a, st);
+  } else {
+    launch_sa_plain_mfma<T, D, C1, C2>(a, st);
+  }
+  return launch_status("dvcp_sa_group_mlp(mfma)");
+}
 
-// the three-layer table (sa1) on the matrix cores (sa_mlp_mfma.hip)
-template <typename T, typename FT, int D>
-int launch_sa3_mfma(const void* xyz, int64_t sb, int64_t sc, int64_t sn, const void* c, int64_t cb, int64_t cc,
-                    int64_t cn, int S, int B, const void* feat, int64_t fb, int64_t fd, int64_t fn, const int32_t* count,
-                    const int32_t* list, int nsample, const float* params, float* out, hipStream_t st);
-
-#ifndef DVCP_SA1_MFMA
-#define DVCP_SA1_MFMA 1
-#endif
-
-template <typename T, typename FT, int D, int C1, int C2, int C3>
+template <typename T, typename FT, int D, int C1, int C2>
 static int launch_sa(const void* xyz, int64_t sb, int64_t sc, int64_t sn, const void* c, int64_t cb, int64_t cc,
                      int64_t cn, int S, int B, const void* feat, int64_t fb, int64_t fd, int64_t fn,
                      const int32_t* count, const int32_t* list, int nsample, const float* params, float* out,
                      hipStream_t st) {
-  if constexpr (DVCP_SA1_MFMA && C1 == 16 && C2 == 16 && C3 == 32 && (D == 0 || D == 3))
-    return launch_sa3_mfma<T, FT, D>(xyz, sb, sc, sn, c, cb, cc, cn, S, B, feat, fb, fd, fn, count, list, nsample,
-                                     params, out, st);
   PointsView<T> pv{static_cast<const T*>(xyz), sb, sc, sn};
   PointsView<T> cv{static_cast<const T*>(c), cb, cc, cn};
   FeatView<FT> fv{static_cast<const FT*>(feat), fb, fd, fn};
   const int cpb = nsample > 64 ? 32 : 8;
   dim3 grid(ceil_div(S, cpb), B);
-  hipLaunchKernelGGL((sa_mlp_kernel<T, FT, D, C1, C2, C3>), grid, dim3(kSaThreads), 0, st, pv, cv, S, fv, count,
+  hipLaunchKernelGGL((sa_mlp_kernel<T, FT, D, C1, C2>), grid, dim3(kSaThreads), 0, st, pv, cv, S, fv, count,
                      list, nsample, cpb, params, out);
   return launch_status("dvcp_sa_group_mlp");
 }
@@ -190,29 +189,29 @@ static int sa_group_mlp_impl(int dtype, const void* xyz, int64_t sb, int64_t sc,
   const bool ff64 = feat_dtype == DVCP_F64;
   float* U = ws ? static_cast<float*>(ws) : nullptr;
   int32_t* order = ws ? reinterpret_cast<int32_t*>(static_cast<char*>(ws) + sa_u_bytes(B, N, chans)) : nullptr;
-#define DVCP_SA(TT, FF, DD, A, Bc, Cc)                                                                     \
-  return dvcp::launch_sa<TT, FF, DD, A, Bc, Cc>(xyz, sb, sc, sn, ctr, cb, cc, cn, S, B, feat, fb, fd, fn, \
-                                                count, list, nsample, params, out, st)
-#define DVCP_SA_T(DD, A, Bc, Cc)                    \
-  do {                                              \
-    if (f64) {                                      \
-      if (ff64) DVCP_SA(double, double, DD, A, Bc, Cc); \
-      DVCP_SA(double, float, DD, A, Bc, Cc);        \
-    }                                               \
-    if (ff64) DVCP_SA(float, double, DD, A, Bc, Cc); \
-    DVCP_SA(float, float, DD, A, Bc, Cc);           \
+#define DVCP_SA(FN, TT, FF, ...)                                                                            \
+  return dvcp::FN<TT, FF, __VA_ARGS__>(xyz, sb, sc, sn, ctr, cb, cc, cn, S, B, feat, fb, fd, fn, count, list, \
+                                       nsample, params, out, st)
+#define DVCP_SA_T(FN, ...)                               \
+  do {                                                   \
+    if (f64) {                                           \
+      if (ff64) DVCP_SA(FN, double, double, __VA_ARGS__); \
+      DVCP_SA(FN, double, float, __VA_ARGS__);           \
+    }                                                    \
+    if (ff64) DVCP_SA(FN, float, double, __VA_ARGS__);   \
+    DVCP_SA(FN, float, float, __VA_ARGS__);              \
   } while (0)
   // The three set-abstraction tables of deep_feat_extraction.py:10-13 (+ REF-R R1).
   if (nlayer == 3 && chans[1] == 16 && chans[2] == 16 && chans[3] == 32) {
-    if (D == 0) DVCP_SA_T(0, 16, 16, 32);
-    if (D == 3) DVCP_SA_T(3, 16, 16, 32);
+    if (D == 0) DVCP_SA_T(launch_sa1_mfma, 0);
+    if (D == 3) DVCP_SA_T(launch_sa1_mfma, 3);
   }
   // the paper-faithful FE's first table (paper supplement: 32-32 on xyz [+ normals]; dvcp.paper)
   if (nlayer == 2 && chans[1] == 32 && chans[2] == 32) {
-    if (D == 0) DVCP_SA_T(0, 32, 32, 0);
-    if (D == 3) DVCP_SA_T(3, 32, 32, 0);
+    if (D == 0) DVCP_SA_T(launch_sa, 0, 32, 32);
+    if (D == 3) DVCP_SA_T(launch_sa, 3, 32, 32);
   }
-  // two-layer tables: fp32 MFMA when each point's features are a contiguous, 16-B aligned fp32 run
+  // two-layer tables: the matrix cores when each point's features are a contiguous, 16-B aligned fp32 run
   const bool mfma_ok = !ff64 && fd == 1 && fb % 4 == 0 && fn % 4 == 0 &&
                        (reinterpret_cast<uintptr_t>(feat) & 15) == 0;
   // a feature row map is applied by the MFMA tables' per-point pre-pass only
@@ -228,11 +227,11 @@ static int sa_group_mlp_impl(int dtype, const void* xyz, int64_t sb, int64_t sc,
                                                     params, U, order, out, rows, Nf, st)
   if (nlayer == 2 && D == 32 && chans[1] == 32 && chans[2] == 64) {
     if (mfma_ok) DVCP_SA_M(32, 32, 64);
-    DVCP_SA_T(32, 32, 64, 0);
+    DVCP_SA_T(launch_sa, 32, 32, 64);
   }
   if (nlayer == 2 && D == 64 && chans[1] == 64 && chans[2] == 64) {
     if (mfma_ok) DVCP_SA_M(64, 64, 64);
-    DVCP_SA_T(64, 64, 64, 0);
+    DVCP_SA_T(launch_sa, 64, 64, 64);
   }
 #undef DVCP_SA_M
 #undef DVCP_SA_T

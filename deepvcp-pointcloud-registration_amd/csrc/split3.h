@@ -1,5 +1,5 @@
 // split3.h -- the fp32-accurate three-way bf16 split that feeds the bf16 matrix cores
-// (sa_mlp_mfma.hip's header gives the derivation and the error bound).
+// (sa_mfma_common.h's header gives the derivation and the error bound).
 //
 // Every fp32 operand is the exact sum of three bf16 pieces, x = x0 + x1 + x2: x0 = bf16(x),
 // x1 = bf16(x - x0), x2 = bf16(x - x0 - x1), each conversion round-to-nearest-even and each
@@ -67,7 +67,7 @@ __device__ __forceinline__ Split3 split3(const float (&x)[8]) {
   return Split3{__builtin_bit_cast(bf16x8, w0), __builtin_bit_cast(bf16x8, w1), __builtin_bit_cast(bf16x8, w2)};
 }
 // The same split of eight values in 12 stages -- pair j = i / 3, piece i % 3 -- of 5, 5 and 1
-// instructions, for a caller that places them one by one between MFMAs (sa_mlp_mfma.hip's
+// instructions, for a caller that places them one by one between MFMAs (sa_mfma_common.h's
 // sa_layer2).  Stage i takes the pair (x[2 j], x[2 j + 1]) again; stages of a pair run in order.
 struct Split3Stages {
   static constexpr int kStages = 12;

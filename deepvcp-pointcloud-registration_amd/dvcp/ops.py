@@ -220,7 +220,7 @@ MFMA_BF16_32X32X16_FLOPS = 2 * 32 * 32 * 16  # one v_mfma_f32_32x32x16_bf16
 def _sa_exec_flops(chans, B, N, S, nsample, count):
     """The flops the kernels execute on this launch, from the ball query's real hit counts
     (evaluated lazily -- after the timed region -- by bench.py: one device reduction of ``count``).
-    Rows run in 16-row half tiles, two per 32-row MFMA tile (csrc/sa_mlp_mfma.hip: a centre takes
+    Rows run in 16-row half tiles, two per 32-row MFMA tile (csrc/sa_mfma_sa1.hip, csrc/sa_mfma_sa2.hip: a centre takes
     ceil(clamp(count, 1, ns) / 16) half tiles; padded rows execute like real ones).
 
     * two-layer MFMA tables (sa2 35-32-64, sa3 67-64-64): layer 1 is split into the per-point pass

@@ -701,7 +701,7 @@ def test_set_abstraction_vs_oracle(cuda, normals, layout, B):
 @pytest.mark.parametrize("table", [0, 1, 2])
 def test_sa_split3_accuracy(cuda, table):
     """The MFMA tables run their bf16 layers as a three-way bf16 split on the matrix cores
-    (csrc/sa_mlp_mfma.hip: layer 2 of sa2 / sa3, layers 2 and 3 of sa1).  On the same groups (the
+    (csrc/sa_mfma_*.hip: layer 2 of sa2 / sa3, layers 2 and 3 of sa1).  On the same groups (the
     GPU ball query's lists) the error against an fp64 evaluation of pointnet2_utils.py:195-200 must
     be of the size of an fp32 evaluation's error (torch fp32 on the CPU, the reference's own
     arithmetic), and within the fp32 tolerance of it.  sa1 (nsample 256) at ~3/4 of nsample hits per
@@ -1057,6 +1057,45 @@ def test_sa_mlp_plain_entry_matches_workspace_entry(cuda):
               st[1], st[2], 64, _lib.ptr(count), _lib.ptr(lst), 64, 2, _lib.ctypes.c_void_p(ch.data_ptr()),
               _lib.ptr(sa.packed_params()), _lib.ptr(plain), _lib.stream())
     torch.testing.assert_close(got_ws, plain, rtol=1e-5, atol=1e-5)
+
+
+@pytest.mark.parametrize("shape", ["flat", "xcd"])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float64], ids=["fp32", "fp64"])
+@pytest.mark.parametrize("table", [1, 2], ids=["sa2", "sa3"])
+def test_sa_mlp_plain_entry_tables(cuda, table, dtype, shape):
+    """dvcp_sa_group_mlp (no workspace) against dvcp_sa_group_mlp_ws on both two-layer tables, fp32
+    and fp64 coordinates, on the hand-built lists of test_gpu_sa_pipeline.py: counts cycling through
+    (0, 1, 15, 16, 17, 31, 32, 33, 63, 64, nsample) along the flat centre index, list rows of centres
+    without hits filled with 1 << 30, N = 300 points within one radius.  (3, 5600): 16,800 centres
+    on a grid that saturates at 16,384 waves, so some waves walk two centres and fetch the second
+    one's first list row while the first one's last tile runs; (8, 2100): the per-XCD index space.
+    Centres without hits are exactly zero from both entries; the others agree within the tolerance
+    of test_sa_mlp_plain_entry_matches_workspace_entry."""
+    import test_gpu_sa_pipeline as SP
+    from dvcp import _lib, ops
+    B, S, _ = SP.SHAPES[shape]
+    N = 300
+    c = SP._make(table, B, S, N, None, rows_variant=False, seed=700 + 10 * table + B)
+    sa, ns = c["mine"].to(cuda), c["ns"]
+    xyz, ctr = c["xyz"].to(cuda, dtype), c["ctr"].to(cuda, dtype)
+    count, lst = c["count"].to(cuda), c["lst"].to(cuda)
+    feat = c["feat"].to(cuda).transpose(1, 2)  # (B, D, N), point-major memory
+    D = feat.shape[1]
+    params = sa.packed_params()
+    got_ws = ops.sa_group_mlp(xyz, ctr, feat, count, lst, ns, sa.chans, params, xyz_pdim=2, feat_ddim=1, feat_pdim=2)
+    ch = torch.tensor(list(sa.chans), dtype=torch.int32)
+    plain = torch.full_like(got_ws, float("nan"))
+    st = feat.stride()
+    _lib.call("dvcp_sa_group_mlp", _lib.F64 if dtype == torch.float64 else _lib.F32, _lib.ptr(xyz), xyz.stride(0),
+              xyz.stride(1), xyz.stride(2), N, _lib.ptr(ctr), ctr.stride(0), ctr.stride(1), ctr.stride(2), S, B,
+              _lib.F32, _lib.ptr(feat), st[0], st[1], st[2], D, _lib.ptr(count), _lib.ptr(lst), ns, 2,
+              _lib.ctypes.c_void_p(ch.data_ptr()), _lib.ptr(params), _lib.ptr(plain), _lib.stream())
+    torch.cuda.synchronize()
+    empty = (count < 1)
+    assert int(empty.sum()) >= B * S // 11
+    assert torch.equal(got_ws[empty], torch.zeros_like(got_ws[empty]))
+    assert torch.equal(plain[empty], torch.zeros_like(plain[empty]))
+    torch.testing.assert_close(plain, got_ws, rtol=1e-5, atol=1e-5)
 
 
 @pytest.mark.parametrize("fix", [True, False])

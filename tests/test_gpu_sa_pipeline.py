@@ -1,4 +1,4 @@
-"""The set-abstraction table kernels (csrc/sa_mlp_mfma.hip) walk each wave's centres as one flat
+"""The set-abstraction table kernels (csrc/sa_mfma_sa1.hip, _sa2.hip, _sa3.hip) walk each wave's centres as one flat
 tile sequence and prefetch: the list entry of tile t + 2 and the gathered U row / point of tile
 t + 1 are in flight while tile t runs.  These tests pin what such a pipeline can get wrong: a tile
 fed another tile's gathered rows, centre or running maximum, a prefetch through the list row of a

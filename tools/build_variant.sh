@@ -1,5 +1,5 @@
 #!/bin/bash
-# Build an A/B variant library: one source recompiled with extra -D flags, linked with the in-tree
+# Build an A/B variant library: one source recompiled with the Makefile's flags for it plus extra -D flags, linked with the in-tree
 # objects of every other source, into dvcp/libdvcp_hip_<name>.so (loaded by tools/gpu_ab_*.sh
 # through DVCP_LIB_PATH; the in-tree library is not touched).  Delete the variants before a round
 # ends (they travel with every gpurun call).
@@ -11,9 +11,10 @@ make -s -j8
 HIPFLAGS="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -mcode-object-version=5 -ffp-contract=off \
   -fhip-fp32-correctly-rounded-divide-sqrt -Wall -Wno-unused-function -I../include"
 case $stem in
-  fps) EXTRA="-mllvm -amdgpu-promote-alloca-to-vector-limit=2048 -fno-slp-vectorize" ;;
+  fps|fps_*) EXTRA="-mllvm -amdgpu-promote-alloca-to-vector-limit=2048 -fno-slp-vectorize" ;;
   knn_tiled|knn_tiled_*) EXTRA="-mllvm -amdgpu-promote-alloca-to-vector-limit=2048" ;;
   sa_bn) EXTRA="-mllvm -amdgpu-promote-alloca-to-vector-limit=4096" ;;
+  sa_mfma_*|sa_bn_mfma|sa_bwd) EXTRA="-fno-slp-vectorize" ;;
   *) EXTRA="" ;;
 esac
 mkdir -p build/var

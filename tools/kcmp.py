@@ -1,13 +1,16 @@
 #!/usr/bin/env python3
 """Compare the kernels of gfx950 code objects function by function.
 
-Usage: tools/kcmp.py OLD.co NEW.co [NEW2.co ...]
+Usage: tools/kcmp.py [--rename 'OLD_PREFIX=NEW_PREFIX' ...] OLD.co NEW.co [NEW2.co ...]
 
 Each argument is a device code object (hipcc --offload-device-only -c, as tools/kres.sh builds
 one) or an offload bundle, which is unbundled for gfx950 first.  The kernels of the NEW objects
 together are compared with OLD's: every kernel (a function with a `.kd` descriptor) is
 disassembled with llvm-objdump -d and its whole text -- mnemonics, operands and encodings, the
-address column dropped -- must match.  Prints the identical, differing, missing (only in OLD) and
+address column dropped -- must match.  A kernel's own symbol in the comments of its branches
+(`<symbol+0x...>`) is dropped too, so a renamed kernel still compares.  --rename (repeatable)
+replaces OLD_PREFIX at the start of OLD's demangled kernel names by NEW_PREFIX before the names are
+matched, for kernels that were renamed or whose template list changed.  Prints the identical, differing, missing (only in OLD) and
 added (only in NEW) kernels, a kernel found in two NEW objects, and exits 1 unless every kernel of
 NEW is identical to OLD's.
 """
@@ -50,18 +53,33 @@ def kernels(path, tmp):
             funcs[name] = []
         elif name is not None and ln.strip() and ln.strip() != "...":  # "...": zero padding up to the next symbol
             # "\tinsn operands  // 000000001234: ENCODING ..." -> drop the address
-            funcs[name].append(re.sub(r"//\s*[0-9A-Fa-f]+:", "//", ln).strip())
+            ln = re.sub(r"//\s*[0-9A-Fa-f]+:", "//", ln).strip()
+            funcs[name].append(ln.replace(f"<{name}+", "<+"))  # branch targets: offset only
     names = sorted(kds)
     filt = shutil.which("llvm-cxxfilt", path=LLVM) or shutil.which("llvm-cxxfilt") or shutil.which("c++filt")
     pretty = run(filt, *names).splitlines() if names and filt else names
     return {p: "\n".join(funcs.get(n, ["<no text>"])) for n, p in zip(names, pretty)}
 
 
+def renamed(name, renames):
+    for a, b in renames:
+        if name.startswith(a):
+            return b + name[len(a):]
+    return name
+
+
 def main(argv):
+    renames = []
+    while len(argv) > 2 and argv[1] == "--rename":
+        a, sep, b = argv[2].partition("=")
+        if not sep:
+            sys.exit(__doc__)
+        renames.append((a, b))
+        del argv[1:3]
     if len(argv) < 3:
         sys.exit(__doc__)
     with tempfile.TemporaryDirectory() as tmp:
-        old = kernels(argv[1], tmp)
+        old = {renamed(k, renames): text for k, text in kernels(argv[1], tmp).items()}
         new, twice = {}, []
         for p in argv[2:]:
             for k, text in kernels(p, tmp).items():

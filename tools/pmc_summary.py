@@ -31,8 +31,8 @@ ENTRY = {
     "dvcp_fps_pair": (["fps_pair_kernel"], ["fps_pair_remap_kernel", "fps_select_gated_kernel"]),
     "dvcp_knn_tiled": (["knn_tiled_query_kernel", "knn_sel_query_kernel"],
                        ["knn_tiled_build_kernel", "knn_qbox_kernel", "knn_qhist_kernel", "knn_qscan_kernel"]),
-    "dvcp_sa_group_mlp_ws": (["sa3_mfma_kernel<", "sa_mlp_mfma_kernel<float, 32,"], ["sa_pre_mfma_kernel<32,", "sa_order_kernel"]),
-    "dvcp_sa_group_mlp_rows_ws": (["sa_mlp_mfma_kernel<float, 64,"], ["sa_pre_mfma_kernel<64,"]),
+    "dvcp_sa_group_mlp_ws": (["sa1_mfma_kernel<", "sa2_mfma_kernel<"], ["sa_pre_mfma_kernel<32,", "sa_order_kernel"]),
+    "dvcp_sa_group_mlp_rows_ws": (["sa3_mfma_kernel<"], ["sa_pre_mfma_kernel<64,"]),
     "dvcp_ball_query_ws": (["bq_tiled_kernel", "bq_wave_kernel", "ball_query_kernel"], ["bq_build_kernel", "bq_pack_kernel"]),
     "dvcp_dfe_tgt": (["dfe_tgt"], ["points_pack4_kernel"]),
     "dvcp_cpg": (["cpg_kernel"], []),
