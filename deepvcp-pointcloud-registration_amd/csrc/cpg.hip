@@ -499,7 +499,8 @@ __global__ __launch_bounds__(kCpgThreads) void cpg_kernel(const float* __restric
 extern "C" int dvcp_cpg(const float* src, const float* tgt, int64_t t_p, int64_t t_f, int64_t t_c, const float* cand,
                         int P, int G, const float* params, float* vcp, float* weight, void* stream) {
   DVCP_REQUIRE(src && tgt && cand && params && vcp, "dvcp_cpg: null pointer");
-  DVCP_REQUIRE(G >= 1 && G * G * G <= dvcp::kCpgMaxC, "dvcp_cpg: grid side G=%d unsupported (C <= 1331)", G);
+  DVCP_REQUIRE(G >= 1 && G * G * G <= dvcp::kCpgMaxC,
+               "dvcp_cpg: grid side G=%d unsupported (C <= 1331; dvcp_cpg_tiled takes G <= 32)", G);
   if (P <= 0) return DVCP_OK;
   if (dvcp::cpg_balanced(G * G * G))
     hipLaunchKernelGGL(dvcp::cpg_kernel<true>, dim3(P), dim3(dvcp::kCpgThreads), 0, static_cast<hipStream_t>(stream),

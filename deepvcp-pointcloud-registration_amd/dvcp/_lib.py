@@ -56,6 +56,7 @@ SIGNATURES = {
     "dvcp_dfe_tgt_f16": [_I, _P, _L, _L, _L, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P],
     "dvcp_dfe_tgt_literal": [_I, _P, _L, _L, _L, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P],
     "dvcp_cpg": [_P, _P, _L, _L, _L, _P, _I, _I, _P, _P, _P, _P],
+    "dvcp_cpg_tiled": [_P, _P, _L, _L, _L, _P, _I, _I, _P, _P, _P, _P, _L, _P],
     "dvcp_rigid_transform": [_P, _P, _I, _I, _P, _P, _P],
     "dvcp_paper_pose": [_P, _P, _P, _I, _I, _I, _D, _P, _P, _P, _P, _P, _P],
     "dvcp_paper_pose_backward": [_P, _P, _P, _I, _I, _I, _D, _P, _P, _D, _P, _P, _P, _P],
@@ -136,6 +137,8 @@ def load():
     lib.dvcp_sa_bn_rows_floats.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
     lib.dvcp_sa_bn_zrows_floats.restype = ctypes.c_int64
     lib.dvcp_sa_bn_zrows_floats.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
+    lib.dvcp_cpg_tiled_workspace_bytes.restype = ctypes.c_int64
+    lib.dvcp_cpg_tiled_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int]
     lib.dvcp_cpg1d_nparams.restype = ctypes.c_int
     lib.dvcp_cpg1d_nparams.argtypes = []
     lib.dvcp_sa_bn_pack_floats.restype = ctypes.c_int64
@@ -165,7 +168,7 @@ def exported_symbols():
             "dvcp_fe_head_backward_workspace_bytes", "dvcp_sa_bn_workspace_bytes",
             "dvcp_sa_bn_pack_floats", "dvcp_sa_bn_rows_floats", "dvcp_sa_bn_feat_workspace_bytes", "dvcp_sa_bn_zrows_floats",
             "dvcp_cpg1d_nparams", "dvcp_sa_bnm_supported", "dvcp_sa_bnm_workspace_bytes",
-            "dvcp_fps_pair_workspace_bytes", "dvcp_fps_workspace_bytes"] + list(SIGNATURES)
+            "dvcp_fps_pair_workspace_bytes", "dvcp_fps_workspace_bytes", "dvcp_cpg_tiled_workspace_bytes"] + list(SIGNATURES)
 
 
 # When a list, every entry-point call appends (name, start_event, end_event, work) recorded on

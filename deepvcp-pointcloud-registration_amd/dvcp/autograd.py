@@ -227,8 +227,18 @@ def dfe_tgt(ref_xyz, ref_feat, cand, dist, idx, dfe_module):
     return _DfeTgt.apply(ref_xyz, ref_feat, cand, dist, idx, *_linears(dfe_module))
 
 
+def require_trainable_grid(G):
+    """Grids above 11^3 take the tiled CPG forward (dvcp_cpg_tiled), which has no backward: say so
+    when the forward is recorded, not from dvcp_cpg_backward in the middle of loss.backward()."""
+    if ops.cpg_method(G) != "lds":
+        raise NotImplementedError(
+            f"dvcp: candidate grids above {ops.CPG_LDS_MAX_G}^3 are inference-only (G={int(G)}): the large-grid CPG "
+            f"has no backward.  Run under torch.no_grad(), or train with int(2r/s + 1) <= {ops.CPG_LDS_MAX_G}")
+
+
 def cpg(src, tgt, cand, G, cpg_module):
-    """cpg.py:27-60, differentiable in src, tgt and the conv weights."""
+    """cpg.py:27-60, differentiable in src, tgt and the conv weights (G <= 11)."""
+    require_trainable_grid(G)
     convs = [cpg_module.conv1, cpg_module.conv2, cpg_module.conv3]
     return _Cpg.apply(src, tgt, cand, G, *[t for c in convs for t in (c.weight, c.bias)])
 

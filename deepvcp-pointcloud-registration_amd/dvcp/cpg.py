@@ -2,7 +2,9 @@
 
 Cost volume (src - tgt)^2 with the reference's reshape of the permuted target (Q11), Conv3d
 32-16-4-1 (k3, p1, no activations), softmax over the C = G^3 candidates, weighted mean of the
-candidates.  One gfx950 workgroup per key point (dvcp_cpg).
+candidates.  One gfx950 workgroup per key point (dvcp_cpg) up to G = 11; grids of 12 <= G <= 32
+are cut into blocks staged through a workspace (dvcp_cpg_tiled).  G <= 32; training G <= 11: the
+large-grid path has no backward, and a forward that records autograd raises NotImplementedError.
 """
 import torch
 import torch.nn as nn

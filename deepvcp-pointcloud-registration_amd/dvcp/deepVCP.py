@@ -46,7 +46,11 @@ def _warn_f16_autograd():
 class DeepVCP(nn.Module):
     def __init__(self, use_normal, K=64, r=1.0, s=0.4, fe_npoint=10000, feat_dtype=torch.float32, dfe_literal=False,
                  fps_parts=None):
-        """``feat_dtype``: storage of the target feature table the fused target stage gathers
+        """``r``, ``s``: the candidate grid's search radius and voxel edge; its side
+        G = int(2r/s + 1) must be <= 32, and <= 11 to train (larger grids take the tiled CPG
+        forward, dvcp_cpg_tiled, which is inference-only: a forward that records autograd raises
+        NotImplementedError).
+        ``feat_dtype``: storage of the target feature table the fused target stage gathers
         (torch.float16: BASELINE C5's "fp16 features", dvcp_dfe_tgt_f16; inference only -- the
         reference keeps fp32 features, so float16 is not reference precision).
         ``dfe_literal``: the fused target DFE chains fc1, fc2, fc3 as written (dvcp_dfe_tgt_literal,
@@ -185,6 +189,8 @@ class DeepVCP(nn.Module):
         ``return_weights``: also return the key points' weighting-layer scores (B, K), the
         weights of the paper's weighted pose solve (dvcp.paper)."""
         train_head, train_fe = self._training_mode()
+        if train_head:
+            autograd.require_trainable_grid(int((2 * self.r) / self.s + 1))   # before any launch
         tr = {} if (return_weights and trace is None) else trace
         with _lib.deferred_flags():  # the guards' host copies once, after the step's launches
             feats = self.extract_features(src_pts, tgt_pts, starts, train_fe=train_fe, trace=trace)
@@ -199,6 +205,8 @@ class DeepVCP(nn.Module):
         B = src_xyz.shape[0]
         K, r, s = self.K, self.r, self.s
         dev = src_xyz.device
+        if train_head:
+            autograd.require_trainable_grid(int((2 * r) / s + 1))   # large grids: inference only
         _lib.check_device_flags()   # guards of earlier launches (non-blocking)
         top = ops.topk(score, K) if keypoint_idx is None else keypoint_idx.to(dev, torch.int64).contiguous()
         if train_head and src_feat.requires_grad:

@@ -454,24 +454,79 @@ def _dfe_tgt_exec(literal, cands):
 MFMA_BF16_16X16X32_FLOPS = 2 * 16 * 16 * 32  # one v_mfma_f32_16x16x32_bf16
 
 
-def cpg(src, tgt, cand, G, params, want_weight=False):
+CPG_LDS_MAX_G = 11     # dvcp_cpg: the whole grid of a key point in one workgroup's LDS (csrc/cpg.hip)
+CPG_TILED_MAX_G = 32   # dvcp_cpg_tiled: blocks staged through a workspace (csrc/cpg_tiled.hip), inference only
+
+
+def cpg_method(G):
+    """The CPG forward a grid side takes: "lds" (dvcp_cpg) up to 11, "tiled" (dvcp_cpg_tiled) for
+    12..32; ValueError above."""
+    G = int(G)
+    if G > CPG_TILED_MAX_G:
+        raise ValueError(f"cpg: grid side G={G} unsupported: the candidate grid takes G <= {CPG_TILED_MAX_G} "
+                         f"(C <= {CPG_TILED_MAX_G ** 3}); choose r, s with int(2r/s + 1) <= {CPG_TILED_MAX_G}")
+    return "lds" if G <= CPG_LDS_MAX_G else "tiled"
+
+
+def cpg(src, tgt, cand, G, params, want_weight=False, method=None):
     """cpg.py:27-60.  src (B, K, 32) or (B, K, 1, 32); tgt: the reference's (B, K, 32, C)
-    (any strides); cand (B, K, C, 3).  Returns vcp (B, K, 3) [, weights (B, K, C)]."""
+    (any strides); cand (B, K, C, 3).  Returns vcp (B, K, 3) [, weights (B, K, C)].
+    ``method``: None (``cpg_method(G)``), "lds" (G <= 11) or "tiled" (any G <= 32: tests, A/B)."""
     _lib.require_gpu(src, tgt, cand, params)
     B, K, C, _ = cand.shape
     if tgt.dim() != 4 or tuple(tgt.shape) != (B, K, 32, C):
         raise RuntimeError(f"cpg: tgt_dfe_feat must be (B, K, 32, C), got {tuple(tgt.shape)}")
+    G = int(G)
+    auto = cpg_method(G)
+    method = auto if method is None else method
+    if method not in ("lds", "tiled"):
+        raise ValueError(f"dvcp: unknown CPG method {method!r} (lds or tiled)")
     if tgt.stride(0) != K * tgt.stride(1):
         tgt = tgt.contiguous()
     srcc = src.reshape(B * K, 32).contiguous().float()
     candc = cand.contiguous()
     vcp = torch.empty(B, K, 3, dtype=torch.float32, device=cand.device)
     w = torch.empty(B, K, C, dtype=torch.float32, device=cand.device) if want_weight else None
-    call("dvcp_cpg", ptr(srcc), ptr(tgt), tgt.stride(1), tgt.stride(2), tgt.stride(3), ptr(candc), B * K, int(G),
-         ptr(params), ptr(vcp), ptr(w), stream(),
-         work=(2.0 * 27 * (32 * 16 + 16 * 4 + 4) * B * K * C, B * K * (128 + C * (128 + 12) + 12),
-               _cpg_exec(B * K, C)))
+    algo = (2.0 * 27 * (32 * 16 + 16 * 4 + 4) * B * K * C, B * K * (128 + C * (128 + 12) + 12))
+    if method == "lds":
+        call("dvcp_cpg", ptr(srcc), ptr(tgt), tgt.stride(1), tgt.stride(2), tgt.stride(3), ptr(candc), B * K, G,
+             ptr(params), ptr(vcp), ptr(w), stream(), work=algo + (_cpg_exec(B * K, C),))
+    else:
+        nbytes = int(_lib.load().dvcp_cpg_tiled_workspace_bytes(B * K, G))
+        ws = torch.empty(max(4, nbytes // 4), dtype=torch.float32, device=cand.device)
+        flops, traffic = _cpg_tiled_exec(B * K, G, ordered=tgt.stride(2) == C and tgt.stride(3) == 1)
+        call("dvcp_cpg_tiled", ptr(srcc), ptr(tgt), tgt.stride(1), tgt.stride(2), tgt.stride(3), ptr(candc), B * K, G,
+             ptr(params), ptr(vcp), ptr(w), ptr(ws), ws.numel() * 4, stream(),
+             work=(algo[0], algo[1] + traffic, flops))
     return (vcp, w) if want_weight else vcp
+
+
+def _cpg_blocks(G, edge):
+    """Blocks (origin, extent) along one axis of the tiled CPG: ceil(G / edge) blocks of
+    ceil(G / blocks) cells, the last one shorter."""
+    nb = -(-G // edge)
+    bs = -(-G // nb)
+    return [(o, min(bs, G - o)) for o in range(0, G, bs)]
+
+
+def _cpg_tiled_exec(P, G, ordered=False):
+    """Executed work of the tiled CPG forward (csrc/cpg_tiled.hip): (bench.py's 4-tuple, workspace
+    bytes moved).  conv1: per key point and block of <= 11^3 cells, 16-voxel tiles x 4 quarters x 7
+    k-steps of split-3 v_mfma_f32_16x16x32_bf16 (a block's last tile and the zero tap are padding; the
+    halo cells are built, not multiplied); conv2 on the <= 9^3 blocks plus their one-cell halo and
+    conv3 on VALU.  Workspace: the target block written and read once more in Q11 order (unless it
+    arrives ``ordered``: a contiguous (B, K, 32, C) tensor), h1 written once (64 B per cell) and
+    read with a two-cell halo per conv2 block, the logits written and read twice."""
+    b1 = [b for _, b in _cpg_blocks(G, 11)]
+    b2 = [b for _, b in _cpg_blocks(G, 9)]
+    h2 = [min(G, o + b + 2) - max(0, o - 2) for o, b in _cpg_blocks(G, 9)]   # h1 cells read, in the grid
+    tiles = sum(-(-(x * y * z) // 16) for z in b1 for y in b1 for x in b1)
+    conv1 = float(P) * tiles * 4 * 7 * MFMA_BF16_16X16X32_FLOPS
+    c2 = sum((x + 2) * (y + 2) * (z + 2) for z in b2 for y in b2 for x in b2)
+    rest = 2.0 * 27 * P * (16 * 4 * c2 + 4 * G ** 3)
+    h1_read = sum(x * y * z for z in h2 for y in h2 for x in h2)
+    traffic = P * (64 * (G ** 3 + h1_read) + 12 * G ** 3 + (0 if ordered else 256 * G ** 3))
+    return (conv1 + rest, conv1, conv1, 6.0 * conv1), traffic
 
 
 def _cpg_exec(P, C):

@@ -488,10 +488,25 @@ int dvcp_cpg1d_nparams(void);
  * src: P x 32 fp32 (P = B*K key points); tgt: the reference's (B,K,32,C) tensor given by
  * element strides (t_p per key point, t_f per feature, t_c per candidate);
  * cand: P x C x 3 fp32; params: conv1.W(16x32x27), conv1.b, conv2.W(4x16x27), conv2.b,
- * conv3.W(1x4x27), conv3.b.  out: P x 3 fp32; weight (optional): P x C softmax weights. */
+ * conv3.W(1x4x27), conv3.b.  out: P x 3 fp32; weight (optional): P x C softmax weights.
+ * One workgroup per key point with the whole grid in LDS: 1 <= G <= 11 (C <= 1331); larger grids
+ * take dvcp_cpg_tiled. */
 int dvcp_cpg(const float* src, const float* tgt, int64_t t_p, int64_t t_f, int64_t t_c,
              const float* cand, int P, int G, const float* params, float* vcp, float* weight,
              void* stream);
+/* Corresponding point generation on large grids, 1 <= G <= 32 (C <= 32768), inference only (there
+ * is no matching backward).  dvcp_cpg's arguments, packed parameter layout and results (the same
+ * values within fp32 rounding: the summation order differs); the grid is cut into blocks and the
+ * convolutions are staged through ws: conv1's output, the logits and the target block copied into
+ * the order conv1 reads it in, 49 C floats per key point, 16-byte aligned.  The key points are
+ * walked in chunks of ws_bytes / (196 C) on the stream, so any ws that holds one key point will
+ * do; dvcp_cpg_tiled_workspace_bytes(P, G) is the size that gives the fewest launches under a
+ * 256 MiB cap (41 key points per chunk at G = 32, 147 at G = 21), and 0 for P <= 0 or an
+ * unsupported G.  P = 0 is a no-op. */
+int64_t dvcp_cpg_tiled_workspace_bytes(int P, int G);
+int dvcp_cpg_tiled(const float* src, const float* tgt, int64_t t_p, int64_t t_f, int64_t t_c,
+                   const float* cand, int P, int G, const float* params, float* vcp, float* weight,
+                   float* ws, int64_t ws_bytes, void* stream);
 
 /* Kabsch.  Replaces deepVCP_loss.py:13-44 get_rigid_transform: x, y: B x 3 x n fp64
  * (contiguous) -> R: B x 3 x 3, t: B x 3 x 1 (fp64). R = V U^T, no reflection fix (Q13).

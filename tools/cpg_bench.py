@@ -1,0 +1,88 @@
+"""CPG micro-benchmark: ``ops.cpg`` in isolation at P = 512 key points (B = 8, K = 64), on the
+one-workgroup LDS kernel (dvcp_cpg, G = 11), on the tiled path forced at the same grid, and on the
+tiled path's own grids (dvcp_cpg_tiled, G = 13, 17, 21, 32).  Random inputs in the forward's
+layout (the permuted view of a (B, K, C, 32) tensor; --layout contiguous: a contiguous
+(B, K, 32, C) tensor, which the tiled path takes without its ordering pre-pass), random-init
+weights.  Prints the median ms per call over repeated launches (HIP events, after a warm-up) and
+ns per voxel; the yardstick for the tiled path is the LDS kernel's ns per voxel in the same run.
+
+    python tools/cpg_bench.py [--P 512] [--reps 20] [--grids 21,32] [--layout permuted] [--out FILE]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.join(os.path.dirname(__file__), "..", "deepvcp-pointcloud-registration_amd"))
+
+CASES = [(11, "lds"), (11, "tiled"), (13, "tiled"), (17, "tiled"), (21, "tiled"), (32, "tiled")]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--P", type=int, default=512, help="key points (a multiple of 64: B x 64)")
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--grids", default="",
+                    help="comma-separated grid sides to run besides the G = 11 LDS yardstick (default: all cases)")
+    ap.add_argument("--layout", choices=["permuted", "contiguous"], default="permuted")
+    ap.add_argument("--out", default=None, help="also write the rows as JSON lines")
+    args = ap.parse_args()
+    import dvcp
+    from dvcp import ops
+    if not torch.cuda.is_available():
+        raise SystemExit("cpg_bench: no GPU (there is no CPU fallback to time)")
+    dev = torch.device("cuda", 0)
+    torch.manual_seed(0)
+    params = dvcp.cpg().to(dev).packed_params()
+    K = 64
+    B = max(1, args.P // K)
+    rows, base = [], None
+    only = {int(x) for x in args.grids.split(",") if x}
+    for G, method in CASES:
+        if only and G not in only and (G, method) != CASES[0]:   # the yardstick row always runs
+            continue
+        C = G ** 3
+        g = torch.Generator(device=dev).manual_seed(G)
+        src = torch.randn(B, K, 32, device=dev, generator=g)
+        tgt = torch.randn(B, K, C, 32, device=dev, generator=g).permute(0, 1, 3, 2)
+        if args.layout == "contiguous":
+            tgt = tgt.contiguous()
+        cand = torch.randn(B, K, C, 3, device=dev, generator=g)
+        with torch.no_grad():
+            for _ in range(args.warmup):
+                out = ops.cpg(src, tgt, cand, G, params, method=method)
+            torch.cuda.synchronize()
+            times = []
+            for _ in range(args.reps):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                ops.cpg(src, tgt, cand, G, params, method=method)
+                e1.record()
+                torch.cuda.synchronize()
+                times.append(e0.elapsed_time(e1))
+        ms = statistics.median(times)
+        ns_vox = ms * 1e6 / (B * K * C)
+        if base is None:
+            base = ns_vox
+        ws = int(dvcp.load_library().dvcp_cpg_tiled_workspace_bytes(B * K, G)) if method == "tiled" else 0
+        row = dict(G=G, method=method, layout=args.layout, P=B * K, C=C, ms=round(ms, 4), ms_min=round(min(times), 4),
+                   ms_max=round(max(times), 4), ns_per_voxel=round(ns_vox, 4), vs_lds_g11=round(ns_vox / base, 2),
+                   workspace_mib=round(ws / 2 ** 20, 1), checksum=float(out.double().sum()))
+        rows.append(row)
+        print(f"G={G:2d} {method:5s} {args.layout} P={B * K}: {ms:8.4f} ms/call (min {min(times):.4f}, max {max(times):.4f})  "
+              f"{ns_vox:.4f} ns/voxel  x{ns_vox / base:.2f} of lds G=11  ws {ws / 2 ** 20:.1f} MiB  "
+              f"checksum {row['checksum']:.9e}", flush=True)
+        del src, tgt, cand
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            for row in rows:
+                f.write(json.dumps(row) + "\n")
+
+
+if __name__ == "__main__":
+    main()
