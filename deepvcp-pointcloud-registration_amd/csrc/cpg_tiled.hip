@@ -1,5 +1,6 @@
 // cpg_tiled.hip -- corresponding point generation (cpg.py:27-60) for candidate grids above the
-// one-workgroup kernel's 11^3 (cpg.hip): 1 <= G <= 32, inference only.
+// one-workgroup kernel's 11^3 (cpg.hip): 1 <= G <= 32.  Backward: cpg_tiled_bwd.hip, which repeats
+// launches 0-2 through ct_forward_chunk (cpg_tiled.h).
 //
 // The grid is cut into blocks and the three convolutions are staged through an HBM workspace
 // (49 C floats per key point: conv1's output h1, cell-major [g][16], the C logits, and the target
@@ -27,67 +28,17 @@
 // Q11 (the reference's reshape of the permuted target): cost cell g, channel f' is element
 // l = 32 g + f' of the (32, C) view, (f = l / C, c = l % C).  l < 2^20 is outside FastDiv's range
 // (x < 2^16); launch 0 walks (f, c) and conv1 walks l, so neither divides.
-#include "common.h"
-#include "cpg_grid.h"
+#include "cpg_tiled.h"
 #include "split3.h"
 
 namespace dvcp {
 
-constexpr int kCtThreads = 1024;                 // 16 waves: LDS allows one workgroup per CU
-constexpr int kCtMaxG = 32;
 constexpr int kCtB1 = 11;                        // conv1 block edge (output cells)
 constexpr int kCtB2 = 9;                         // conv2/conv3 block edge (logits)
 constexpr int kCtPV = 13 * 13 * 13;              // cells of a haloed block, both launches
 constexpr int kCtT = (kCtB1 * kCtB1 * kCtB1 + 15) / 16;  // 16-voxel tiles of a conv1 block
 constexpr int kCtW = kCtThreads / 64;
 constexpr int kCtTW = (kCtT + kCtW - 1) / kCtW;  // tiles per wave
-// Workspace cap: key points are walked in chunks whose workspace fits 256 MiB (41 key points at
-// G = 32, 147 at G = 21: over a thousand conv1 workgroups per launch either way).
-constexpr int64_t kCtWsCap = int64_t(256) << 20;
-
-__host__ __device__ inline int ct_blocks(int G, int edge) { return (G + edge - 1) / edge; }
-__host__ __device__ inline int ct_block_size(int G, int nb) { return (G + nb - 1) / nb; }
-inline int64_t ct_ws_per_point(int G) { return int64_t(49) * G * G * G * 4; }
-
-// FastDiv's multipliers for every row length and plane size a launch's blocks can have, formed on
-// the host (in the kernel each would be a 64-bit division per thread).  An axis has two extents,
-// e[0] = bs and the last block's e[1] = G - (nb - 1) bs; with a halo of h cells on each side
-// (h = 0, 1, 2) a row is e[xl] + 2 h cells long and a plane (e[xl] + 2 h)(e[yl] + 2 h).
-struct CtMagic {
-  uint32_t row[3][2], plane[3][2][2];
-};
-inline CtMagic ct_magic(int G, int nb, int bs) {
-  const int e[2] = {bs, G - (nb - 1) * bs};
-  CtMagic k;
-  for (int h = 0; h < 3; ++h)
-    for (int xl = 0; xl < 2; ++xl) {
-      k.row[h][xl] = FastDiv::magic(e[xl] + 2 * h);
-      for (int yl = 0; yl < 2; ++yl) k.plane[h][xl][yl] = FastDiv::magic((e[xl] + 2 * h) * (e[yl] + 2 * h));
-    }
-  return k;
-}
-
-// The block's origin and extent along each axis (x fastest), from its index in the nb^3 blocks
-struct CtBlock {
-  int ox, oy, oz, bx, by, bz;
-  int xl, yl;  // the block is the last one along x, y (CtMagic's indices)
-  // division by the block's row length and plane size with a halo of h cells
-  __device__ __forceinline__ FastDiv row(const CtMagic& k, int h) const { return FastDiv(k.row[h][xl], bx + 2 * h); }
-  __device__ __forceinline__ FastDiv plane(const CtMagic& k, int h) const {
-    return FastDiv(k.plane[h][xl][yl], (bx + 2 * h) * (by + 2 * h));
-  }
-  __device__ __forceinline__ CtBlock(int blk, int G, int nb, int bs) {
-    const int iz = blk / (nb * nb), r = blk - iz * nb * nb, iy = r / nb, ix = r - iy * nb;
-    xl = ix == nb - 1;
-    yl = iy == nb - 1;
-    ox = ix * bs;
-    oy = iy * bs;
-    oz = iz * bs;
-    bx = min(bs, G - ox);
-    by = min(bs, G - oy);
-    bz = min(bs, G - oz);
-  }
-};
 
 // Launch 0: out[p][f C + c] = tgt[p][f t_f + c t_c], 32 candidates x 32 features per workgroup
 // through an LDS tile (reads along f, the permuted view's contiguous axis; writes along c).
@@ -385,6 +336,28 @@ __global__ __launch_bounds__(kCtThreads) void cpg_tiled_softmax_kernel(const flo
   }
 }
 
+const float* ct_forward_chunk(const float* src, const float* tgt, int64_t t_p, int64_t t_f, int64_t t_c,
+                              const float* cand, int np, int G, const float* params, float* h1, float* logit,
+                              float* order, float* vcp, float* weight, int64_t* tl_p, hipStream_t s) {
+  const int C = G * G * G;
+  const int nb1 = ct_blocks(G, kCtB1), bs1 = ct_block_size(G, nb1);
+  const int nb2 = ct_blocks(G, kCtB2), bs2 = ct_block_size(G, nb2);
+  const CtMagic magic1 = ct_magic(G, nb1, bs1), magic2 = ct_magic(G, nb2, bs2);
+  const bool ordered = t_f == C && t_c == 1;  // already element l = f C + c
+  const float* tl = ordered ? tgt : order;
+  *tl_p = ordered ? t_p : int64_t(32) * C;
+  if (!ordered)
+    hipLaunchKernelGGL(cpg_tiled_order_kernel, dim3((C + 31) / 32, np), dim3(kCtThreads), 0, s, tgt, t_p, t_f, t_c, C,
+                       order);
+  hipLaunchKernelGGL(cpg_tiled_conv1_kernel, dim3(nb1 * nb1 * nb1, np), dim3(kCtThreads), 0, s, src, tl, *tl_p, G, nb1,
+                     bs1, magic1, params, h1);
+  hipLaunchKernelGGL(cpg_tiled_conv23_kernel, dim3(nb2 * nb2 * nb2, np), dim3(kCtThreads), 0, s, h1, G, nb2, bs2,
+                     magic2, params, logit);
+  if (vcp)
+    hipLaunchKernelGGL(cpg_tiled_softmax_kernel, dim3(np), dim3(kCtThreads), 0, s, logit, cand, C, vcp, weight);
+  return tl;
+}
+
 }  // namespace dvcp
 
 extern "C" int64_t dvcp_cpg_tiled_workspace_bytes(int P, int G) {
@@ -409,26 +382,15 @@ extern "C" int dvcp_cpg_tiled(const float* src, const float* tgt, int64_t t_p, i
   int64_t chunk = ws_bytes / per;
   if (chunk > P) chunk = P;
   if (chunk > 32768) chunk = 32768;  // grid.y
-  const int nb1 = dvcp::ct_blocks(G, dvcp::kCtB1), bs1 = dvcp::ct_block_size(G, nb1);
-  const int nb2 = dvcp::ct_blocks(G, dvcp::kCtB2), bs2 = dvcp::ct_block_size(G, nb2);
-  const dvcp::CtMagic magic1 = dvcp::ct_magic(G, nb1, bs1), magic2 = dvcp::ct_magic(G, nb2, bs2);
   float* h1 = ws;
   float* logit = ws + chunk * C * 16;
   float* order = logit + chunk * C;
-  const bool ordered = t_f == C && t_c == 1;  // already element l = f C + c
   hipStream_t s = static_cast<hipStream_t>(stream);
   for (int64_t p0 = 0; p0 < P; p0 += chunk) {
     const int np = static_cast<int>(P - p0 < chunk ? P - p0 : chunk);
-    if (!ordered)
-      hipLaunchKernelGGL(dvcp::cpg_tiled_order_kernel, dim3((C + 31) / 32, np), dim3(dvcp::kCtThreads), 0, s,
-                         tgt + p0 * t_p, t_p, t_f, t_c, C, order);
-    hipLaunchKernelGGL(dvcp::cpg_tiled_conv1_kernel, dim3(nb1 * nb1 * nb1, np), dim3(dvcp::kCtThreads), 0, s,
-                       src + p0 * 32, ordered ? tgt + p0 * t_p : order, ordered ? t_p : int64_t(32) * C, G, nb1, bs1,
-                       magic1, params, h1);
-    hipLaunchKernelGGL(dvcp::cpg_tiled_conv23_kernel, dim3(nb2 * nb2 * nb2, np), dim3(dvcp::kCtThreads), 0, s, h1, G,
-                       nb2, bs2, magic2, params, logit);
-    hipLaunchKernelGGL(dvcp::cpg_tiled_softmax_kernel, dim3(np), dim3(dvcp::kCtThreads), 0, s, logit,
-                       cand + p0 * C * 3, C, vcp + p0 * 3, weight ? weight + p0 * C : nullptr);
+    int64_t tl_p;
+    dvcp::ct_forward_chunk(src + p0 * 32, tgt + p0 * t_p, t_p, t_f, t_c, cand + p0 * C * 3, np, G, params, h1, logit,
+                           order, vcp + p0 * 3, weight ? weight + p0 * C : nullptr, &tl_p, s);
   }
   return dvcp::launch_status("dvcp_cpg_tiled");
 }

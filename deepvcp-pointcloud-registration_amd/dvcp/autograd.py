@@ -6,7 +6,7 @@ feature extractor.  Here the head's backward runs in hand-written HIP kernels:
 
   * ``pose_loss``  -- deepVCP_loss.py:105-121 forward (dvcp_svd_optimization) and backward
                       (dvcp_svd_optimization_backward, both Kabsch solves differentiated);
-  * ``cpg``        -- cpg.py:27-60 (dvcp_cpg / dvcp_cpg_backward): gradients for the conv
+  * ``cpg``        -- cpg.py:27-60 (dvcp_cpg / dvcp_cpg_backward; G > 11: the tiled pair): gradients for the conv
                       weights and for both DFE outputs;
   * ``dfe_rows``   -- deep_feat_embedding.py on the source rows (dvcp_dfe / dvcp_dfe_backward);
   * ``dfe_tgt``    -- the fused target rows (dvcp_dfe_tgt / dvcp_dfe_tgt_backward), also
@@ -87,13 +87,15 @@ class _Cpg(torch.autograd.Function):
         params = _pack(weights)
         ctx.save_for_backward(src, tgt, cand, params)
         ctx.G = G
+        ctx.method = ops.cpg_method(G)
         ctx.weights = [(w.shape, w.dtype) for w in weights]
         return ops.cpg(src, tgt, cand, G, params)
 
     @staticmethod
     def backward(ctx, g):
         src, tgt, cand, params = ctx.saved_tensors
-        gsrc, gtgt, gp = ops.cpg_backward(src, tgt, cand, ctx.G, params, g)
+        backward = ops.cpg_backward if ctx.method == "lds" else ops.cpg_tiled_backward
+        gsrc, gtgt, gp = backward(src, tgt, cand, ctx.G, params, g)
         gsrc = gsrc.view(src.shape).to(src.dtype) if ctx.needs_input_grad[0] else None
         gtgt = gtgt.to(tgt.dtype) if ctx.needs_input_grad[1] else None
         return (gsrc, gtgt, None, None, *_split(gp, ctx.weights))
@@ -227,18 +229,22 @@ def dfe_tgt(ref_xyz, ref_feat, cand, dist, idx, dfe_module):
     return _DfeTgt.apply(ref_xyz, ref_feat, cand, dist, idx, *_linears(dfe_module))
 
 
-def require_trainable_grid(G):
-    """Grids above 11^3 take the tiled CPG forward (dvcp_cpg_tiled), which has no backward: say so
-    when the forward is recorded, not from dvcp_cpg_backward in the middle of loss.backward()."""
-    if ops.cpg_method(G) != "lds":
+def require_trainable_grid(G, large_grid=False):
+    """Grids above 11^3 take the tiled CPG (dvcp_cpg_tiled), whose backward (dvcp_cpg_tiled_backward)
+    is opt-in: without ``large_grid`` a forward that records autograd there is refused when it is
+    recorded, not in the middle of loss.backward().  With ``large_grid=True`` every G <= 32 passes
+    (ValueError above, as ``ops.cpg_method``).  The default is meant to flip to True once the test
+    that pins the refusal is retired."""
+    if ops.cpg_method(G) != "lds" and not large_grid:
         raise NotImplementedError(
             f"dvcp: candidate grids above {ops.CPG_LDS_MAX_G}^3 are inference-only (G={int(G)}): the large-grid CPG "
             f"has no backward.  Run under torch.no_grad(), or train with int(2r/s + 1) <= {ops.CPG_LDS_MAX_G}")
 
 
-def cpg(src, tgt, cand, G, cpg_module):
-    """cpg.py:27-60, differentiable in src, tgt and the conv weights (G <= 11)."""
-    require_trainable_grid(G)
+def cpg(src, tgt, cand, G, cpg_module, large_grid=False):
+    """cpg.py:27-60, differentiable in src, tgt and the conv weights: G <= 11 (dvcp_cpg_backward),
+    and with ``large_grid=True`` G <= 32 (12..32: dvcp_cpg_tiled_backward)."""
+    require_trainable_grid(G, large_grid)
     convs = [cpg_module.conv1, cpg_module.conv2, cpg_module.conv3]
     return _Cpg.apply(src, tgt, cand, G, *[t for c in convs for t in (c.weight, c.bias)])
 

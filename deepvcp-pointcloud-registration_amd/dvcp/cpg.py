@@ -3,8 +3,9 @@
 Cost volume (src - tgt)^2 with the reference's reshape of the permuted target (Q11), Conv3d
 32-16-4-1 (k3, p1, no activations), softmax over the C = G^3 candidates, weighted mean of the
 candidates.  One gfx950 workgroup per key point (dvcp_cpg) up to G = 11; grids of 12 <= G <= 32
-are cut into blocks staged through a workspace (dvcp_cpg_tiled).  G <= 32; training G <= 11: the
-large-grid path has no backward, and a forward that records autograd raises NotImplementedError.
+are cut into blocks staged through a workspace (dvcp_cpg_tiled, dvcp_cpg_tiled_backward).  G <= 32.
+Training takes G <= 11 by default: above, a forward that records autograd raises NotImplementedError
+unless the module was built with ``train_large_grid=True``.
 """
 import torch
 import torch.nn as nn
@@ -14,8 +15,13 @@ from ._params import cached_pack
 
 
 class cpg(nn.Module):
-    def __init__(self):
+    def __init__(self, train_large_grid=False):
+        """``train_large_grid``: let a forward that records autograd run on grids of 12 <= G <= 32
+        (backward: dvcp_cpg_tiled_backward).  Off by default, so the present refusal stays as it is;
+        the default is meant to flip once the test that pins the refusal is retired.  A plain
+        attribute: no parameter or buffer, the state_dict is the same either way."""
         super().__init__()
+        self.train_large_grid = bool(train_large_grid)
         self.conv1 = nn.Conv3d(in_channels=32, out_channels=16, kernel_size=3, stride=1, padding=1)
         self.conv2 = nn.Conv3d(in_channels=16, out_channels=4, kernel_size=3, stride=1, padding=1)
         self.conv3 = nn.Conv3d(in_channels=4, out_channels=1, kernel_size=3, stride=1, padding=1)
@@ -33,7 +39,8 @@ class cpg(nn.Module):
         grid_size = int((2 * r) / s + 1)
         assert C == grid_size * grid_size * grid_size
         if not return_weights and _wants_grad(self, src_dfe_feat, tgt_dfe_feat):
-            return autograd.cpg(src_dfe_feat, tgt_dfe_feat, candidates, grid_size, self)
+            return autograd.cpg(src_dfe_feat, tgt_dfe_feat, candidates, grid_size, self,
+                                large_grid=self.train_large_grid)
         return ops.cpg(src_dfe_feat, tgt_dfe_feat, candidates, grid_size, self.packed_params(),
                        want_weight=return_weights)
 

@@ -45,11 +45,20 @@ def _warn_f16_autograd():
 
 class DeepVCP(nn.Module):
     def __init__(self, use_normal, K=64, r=1.0, s=0.4, fe_npoint=10000, feat_dtype=torch.float32, dfe_literal=False,
-                 fps_parts=None):
+                 fps_parts=None, train_large_grid=False):
         """``r``, ``s``: the candidate grid's search radius and voxel edge; its side
-        G = int(2r/s + 1) must be <= 32, and <= 11 to train (larger grids take the tiled CPG
-        forward, dvcp_cpg_tiled, which is inference-only: a forward that records autograd raises
-        NotImplementedError).
+        G = int(2r/s + 1) must be <= 32.  Grids above 11 take the tiled CPG (dvcp_cpg_tiled); they
+        train with ``train_large_grid=True`` (backward: dvcp_cpg_tiled_backward).  Without it a
+        forward that records autograd at G > 11 raises NotImplementedError, as before; the default
+        is meant to flip once the test that pins that refusal is retired.  The flag is a plain
+        attribute of ``self.cpg``, so the state_dict keys do not change.  The rest of the training
+        step takes any number of candidates: the fused target rows' backward (dvcp_dfe_tgt_backward)
+        sizes its workspace from the row count Q = K C and has no cap below G = 32 (593 k rows per
+        pair at G = 21, K = 64; its one limit, B Q < 2^26 when the extractor trains, is 113 such
+        pairs).  What grows with G is memory: with the extractor frozen the workspace stays under
+        10 MB, but when the extractor trains the target-feature gradient takes 4 KiB of workspace
+        per row, 2.4 GB per pair at G = 21, K = 64, beside the (B, K, C, 32) target rows, their
+        gradient and the kNN tables kept for the backward.
         ``feat_dtype``: storage of the target feature table the fused target stage gathers
         (torch.float16: BASELINE C5's "fp16 features", dvcp_dfe_tgt_f16; inference only -- the
         reference keeps fp32 features, so float16 is not reference precision).
@@ -70,7 +79,7 @@ class DeepVCP(nn.Module):
         self.FE1.fps_parts = fps_parts
         self.WL = weighting_layer()
         self.DFE = feat_embedding_layer()
-        self.cpg = cpg()
+        self.cpg = cpg(train_large_grid=train_large_grid)
         self.K, self.r, self.s = K, r, s
 
     def _side_stream(self, dev):
@@ -190,7 +199,8 @@ class DeepVCP(nn.Module):
         weights of the paper's weighted pose solve (dvcp.paper)."""
         train_head, train_fe = self._training_mode()
         if train_head:
-            autograd.require_trainable_grid(int((2 * self.r) / self.s + 1))   # before any launch
+            # before any launch
+            autograd.require_trainable_grid(int((2 * self.r) / self.s + 1), self.cpg.train_large_grid)
         tr = {} if (return_weights and trace is None) else trace
         with _lib.deferred_flags():  # the guards' host copies once, after the step's launches
             feats = self.extract_features(src_pts, tgt_pts, starts, train_fe=train_fe, trace=trace)
@@ -206,7 +216,7 @@ class DeepVCP(nn.Module):
         K, r, s = self.K, self.r, self.s
         dev = src_xyz.device
         if train_head:
-            autograd.require_trainable_grid(int((2 * r) / s + 1))   # large grids: inference only
+            autograd.require_trainable_grid(int((2 * r) / s + 1), self.cpg.train_large_grid)   # large grids: opt-in
         _lib.check_device_flags()   # guards of earlier launches (non-blocking)
         top = ops.topk(score, K) if keypoint_idx is None else keypoint_idx.to(dev, torch.int64).contiguous()
         if train_head and src_feat.requires_grad:
@@ -245,7 +255,8 @@ class DeepVCP(nn.Module):
             if self.feat_dtype != torch.float32:
                 _warn_f16_autograd()
             tgt_dfe = autograd.dfe_tgt(tgt_xyz, tgt_feat, qry, dist, idx, self.DFE).view(B, K, C, 32)
-            vcp = autograd.cpg(src_dfe, tgt_dfe.permute(0, 1, 3, 2), cand, G, self.cpg)
+            vcp = autograd.cpg(src_dfe, tgt_dfe.permute(0, 1, 3, 2), cand, G, self.cpg,
+                               large_grid=self.cpg.train_large_grid)
         else:
             feat_t = tgt_feat if self.feat_dtype == torch.float32 else tgt_feat.to(self.feat_dtype)
             tgt_dfe = ops.dfe_tgt(tgt_xyz, feat_t, qry, dist, idx, dfe_pack, ref_pdim=2,

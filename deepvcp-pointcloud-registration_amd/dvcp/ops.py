@@ -455,7 +455,7 @@ MFMA_BF16_16X16X32_FLOPS = 2 * 16 * 16 * 32  # one v_mfma_f32_16x16x32_bf16
 
 
 CPG_LDS_MAX_G = 11     # dvcp_cpg: the whole grid of a key point in one workgroup's LDS (csrc/cpg.hip)
-CPG_TILED_MAX_G = 32   # dvcp_cpg_tiled: blocks staged through a workspace (csrc/cpg_tiled.hip), inference only
+CPG_TILED_MAX_G = 32   # dvcp_cpg_tiled(_backward): blocks staged through a workspace (csrc/cpg_tiled*.hip)
 
 
 def cpg_method(G):
@@ -696,6 +696,44 @@ def cpg_backward(src, tgt, cand, G, params, grad_vcp):
     call("dvcp_cpg_backward", ptr(srcc), ptr(tgt), tgt.stride(1), tgt.stride(2), tgt.stride(3), ptr(candc), P, int(G),
          ptr(params), ptr(gv), ptr(gsrc), ptr(gtgt), ptr(ws), ptr(gp), stream(),
          work=(3 * 2.0 * 27 * (32 * 16 + 16 * 4 + 4) * P * C, P * (128 + C * (128 + 12 + 128) + 12)))
+    return gsrc, gtgt, gp
+
+
+def cpg_tiled_backward(src, tgt, cand, G, params, grad_vcp, ws_bytes=None):
+    """Gradients of ``cpg`` on any grid side G <= 32 (csrc/cpg_tiled_bwd.hip): ``cpg_backward``'s
+    shapes and results, (d src (B,K,32), d tgt (B,K,32,C), d params), with the grid cut into blocks
+    of <= 8^3 cells staged through a workspace.  ``tgt`` may have any strides.  ``ws_bytes``: the
+    workspace size instead of dvcp_cpg_tiled_backward_workspace_bytes (tests: several chunks of key
+    points; the results do not depend on it)."""
+    _lib.require_gpu(src, tgt, cand, params, grad_vcp)
+    B, K, C, _ = cand.shape
+    if tgt.dim() != 4 or tuple(tgt.shape) != (B, K, 32, C):
+        raise RuntimeError(f"cpg_tiled_backward: tgt_dfe_feat must be (B, K, 32, C), got {tuple(tgt.shape)}")
+    G = int(G)
+    cpg_method(G)   # ValueError above 32
+    if tgt.stride(0) != K * tgt.stride(1):
+        tgt = tgt.contiguous()
+    P = B * K
+    srcc = src.reshape(P, 32).contiguous().float()
+    candc = cand.contiguous()
+    gv = grad_vcp.reshape(P, 3).float().contiguous()
+    dev = cand.device
+    gsrc = torch.empty(B, K, 32, dtype=torch.float32, device=dev)
+    gtgt = torch.empty(B, K, 32, C, dtype=torch.float32, device=dev)
+    nbytes = int(_lib.load().dvcp_cpg_tiled_backward_workspace_bytes(P, G)) if ws_bytes is None else int(ws_bytes)
+    ws = torch.empty(max(4, nbytes // 4), dtype=torch.float32, device=dev)
+    gp = torch.empty(CPG_NPARAMS, dtype=torch.float32, device=dev)
+    nblk = len(_cpg_blocks(G, 8)) ** 3
+    fwd, traffic = _cpg_tiled_exec(P, G, ordered=tgt.stride(2) == C and tgt.stride(3) == 1)
+    algo = 3 * 2.0 * 27 * (32 * 16 + 16 * 4 + 4) * P * C
+    # executed: the forward's launches again, conv2 once more for h2, and the two products of each
+    # convolution's backward on VALU; workspace: h2, dlg, dh2, dh1 written once and read with a
+    # one-cell halo, the blocks' partial sums
+    valu = 2.0 * 27 * P * C * (16 * 4 + 2 * (4 + 16 * 4 + 32 * 16))
+    call("dvcp_cpg_tiled_backward", ptr(srcc), ptr(tgt), tgt.stride(1), tgt.stride(2), tgt.stride(3), ptr(candc), P,
+         G, ptr(params), ptr(gv), ptr(gsrc), ptr(gtgt), ptr(ws), nbytes, ptr(gp), stream(),
+         work=(algo, P * (128 + C * (128 + 12 + 128) + 12) + traffic + P * (4.0 * C * 3 * 41 + 8.0 * nblk * 15713),
+               (fwd[0] + valu, fwd[1], fwd[2], fwd[3])))
     return gsrc, gtgt, gp
 
 

@@ -494,8 +494,8 @@ int dvcp_cpg1d_nparams(void);
 int dvcp_cpg(const float* src, const float* tgt, int64_t t_p, int64_t t_f, int64_t t_c,
              const float* cand, int P, int G, const float* params, float* vcp, float* weight,
              void* stream);
-/* Corresponding point generation on large grids, 1 <= G <= 32 (C <= 32768), inference only (there
- * is no matching backward).  dvcp_cpg's arguments, packed parameter layout and results (the same
+/* Corresponding point generation on large grids, 1 <= G <= 32 (C <= 32768); its backward is
+ * dvcp_cpg_tiled_backward.  dvcp_cpg's arguments, packed parameter layout and results (the same
  * values within fp32 rounding: the summation order differs); the grid is cut into blocks and the
  * convolutions are staged through ws: conv1's output, the logits and the target block copied into
  * the order conv1 reads it in, 49 C floats per key point, 16-byte aligned.  The key points are
@@ -605,6 +605,21 @@ int64_t dvcp_cpg_backward_workspace_bytes(int P);
 int dvcp_cpg_backward(const float* src, const float* tgt, int64_t t_p, int64_t t_f, int64_t t_c,
                       const float* cand, int P, int G, const float* params, const float* grad_vcp,
                       float* grad_src, float* grad_tgt, float* ws, float* grad_params, void* stream);
+/* CPG backward on large grids, 1 <= G <= 32: dvcp_cpg_backward's arguments, packed parameter
+ * layout and results (the same values within fp32 rounding) with dvcp_cpg_tiled's (ws, ws_bytes)
+ * convention.  The forward's h1 and logits are recomputed per chunk of key points by the forward's
+ * own launches; the grid is cut into blocks of <= 8^3 cells and every stage's gradient is staged
+ * through ws.  ws, 16-byte aligned: 15681 floats of parameter partial sums for each of the P key
+ * points (summed in fp64 in key-point order at the end, so grad_params does not depend on the
+ * chunking and is the same from run to run), then the chunk region: 74 C floats per key point plus
+ * 15713 per block.  Any ws that holds the partials and one key point will do;
+ * dvcp_cpg_tiled_backward_workspace_bytes(P, G) caps the chunk region at 256 MiB (19 key points per
+ * chunk at G = 32) and returns 0 for P <= 0 or an unsupported G.  P = 0 only zeroes grad_params. */
+int64_t dvcp_cpg_tiled_backward_workspace_bytes(int P, int G);
+int dvcp_cpg_tiled_backward(const float* src, const float* tgt, int64_t t_p, int64_t t_f, int64_t t_c,
+                            const float* cand, int P, int G, const float* params, const float* grad_vcp,
+                            float* grad_src, float* grad_tgt, float* ws, int64_t ws_bytes,
+                            float* grad_params, void* stream);
 
 #ifdef __cplusplus
 }

@@ -6,7 +6,11 @@ layout (the permuted view of a (B, K, C, 32) tensor; --layout contiguous: a cont
 weights.  Prints the median ms per call over repeated launches (HIP events, after a warm-up) and
 ns per voxel; the yardstick for the tiled path is the LDS kernel's ns per voxel in the same run.
 
-    python tools/cpg_bench.py [--P 512] [--reps 20] [--grids 21,32] [--layout permuted] [--out FILE]
+``--backward`` times the gradients instead, on the same cases: ``ops.cpg_backward`` (dvcp_cpg_backward,
+G = 11: the yardstick) and ``ops.cpg_tiled_backward`` (dvcp_cpg_tiled_backward) forced at G = 11 and on
+G = 13, 17, 21, 32, with a random grad_vcp.
+
+    python tools/cpg_bench.py [--backward] [--P 512] [--reps 20] [--grids 21,32] [--layout permuted] [--out FILE]
 """
 import argparse
 import json
@@ -29,6 +33,8 @@ def main():
     ap.add_argument("--grids", default="",
                     help="comma-separated grid sides to run besides the G = 11 LDS yardstick (default: all cases)")
     ap.add_argument("--layout", choices=["permuted", "contiguous"], default="permuted")
+    ap.add_argument("--backward", action="store_true",
+                    help="time ops.cpg_backward (lds) / ops.cpg_tiled_backward (tiled) instead of the forward")
     ap.add_argument("--out", default=None, help="also write the rows as JSON lines")
     args = ap.parse_args()
     import dvcp
@@ -52,15 +58,25 @@ def main():
         if args.layout == "contiguous":
             tgt = tgt.contiguous()
         cand = torch.randn(B, K, C, 3, device=dev, generator=g)
+        if args.backward:
+            gv = torch.randn(B, K, 3, device=dev, generator=g)
+            fn = ops.cpg_backward if method == "lds" else ops.cpg_tiled_backward
+
+            def run():
+                gsrc, gtgt, gp = fn(src, tgt, cand, G, params, gv)
+                return gp   # (d tgt is P x 32 C floats: the checksum is the parameter gradient's)
+        else:
+            def run():
+                return ops.cpg(src, tgt, cand, G, params, method=method)
         with torch.no_grad():
             for _ in range(args.warmup):
-                out = ops.cpg(src, tgt, cand, G, params, method=method)
+                out = run()
             torch.cuda.synchronize()
             times = []
             for _ in range(args.reps):
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 e0.record()
-                ops.cpg(src, tgt, cand, G, params, method=method)
+                run()
                 e1.record()
                 torch.cuda.synchronize()
                 times.append(e0.elapsed_time(e1))
@@ -68,12 +84,19 @@ def main():
         ns_vox = ms * 1e6 / (B * K * C)
         if base is None:
             base = ns_vox
-        ws = int(dvcp.load_library().dvcp_cpg_tiled_workspace_bytes(B * K, G)) if method == "tiled" else 0
-        row = dict(G=G, method=method, layout=args.layout, P=B * K, C=C, ms=round(ms, 4), ms_min=round(min(times), 4),
+        lib = dvcp.load_library()
+        if args.backward:
+            ws = int(lib.dvcp_cpg_tiled_backward_workspace_bytes(B * K, G) if method == "tiled"
+                     else lib.dvcp_cpg_backward_workspace_bytes(B * K))
+        else:
+            ws = int(lib.dvcp_cpg_tiled_workspace_bytes(B * K, G)) if method == "tiled" else 0
+        row = dict(G=G, method=method, direction="backward" if args.backward else "forward", layout=args.layout,
+                   P=B * K, C=C, ms=round(ms, 4), ms_min=round(min(times), 4),
                    ms_max=round(max(times), 4), ns_per_voxel=round(ns_vox, 4), vs_lds_g11=round(ns_vox / base, 2),
                    workspace_mib=round(ws / 2 ** 20, 1), checksum=float(out.double().sum()))
         rows.append(row)
-        print(f"G={G:2d} {method:5s} {args.layout} P={B * K}: {ms:8.4f} ms/call (min {min(times):.4f}, max {max(times):.4f})  "
+        print(f"{'bwd ' if args.backward else ''}G={G:2d} {method:5s} {args.layout} P={B * K}: {ms:8.4f} ms/call "
+              f"(min {min(times):.4f}, max {max(times):.4f})  "
               f"{ns_vox:.4f} ns/voxel  x{ns_vox / base:.2f} of lds G=11  ws {ws / 2 ** 20:.1f} MiB  "
               f"checksum {row['checksum']:.9e}", flush=True)
         del src, tgt, cand

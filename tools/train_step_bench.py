@@ -8,7 +8,10 @@ One step = model(src, tgt, R_gt, t_init) with autograd on the head -> deepVCP_lo
 Prints one JSON line: pairs/s, ms/step and the per-entry-point HIP-event times of the backward
 kernels (and the forward's) over the timed steps.
 
-    python tools/train_step_bench.py [--steps 10 --warmup 2] [--prefetch P]
+    python tools/train_step_bench.py [--steps 10 --warmup 2] [--prefetch P] [--r 4.0 --s 0.4 --train-large-grid]
+
+--r, --s: the candidate grid (side int(2r/s + 1); the default 2.0, 0.4 is G = 11).  A side above 11
+trains only with --train-large-grid (dvcp.DeepVCP(train_large_grid=True): dvcp_cpg_tiled_backward).
 
 --prefetch P: the frozen feature extractor of the next P batches runs ahead on P streams
 (DeepVCP.extract_features) while the current batch's head trains (DeepVCP.forward_head); the
@@ -41,6 +44,10 @@ def main():
                     help="train FE1 too (frozen-BN: eval-mode BatchNorm, trainable parameters); no prefetch")
     ap.add_argument("--bn-train", action="store_true",
                     help="with --train-fe: FE1 in training mode (batch-statistics BatchNorm, as model.train())")
+    ap.add_argument("--r", type=float, default=2.0, help="candidate grid search radius")
+    ap.add_argument("--s", type=float, default=0.4, help="candidate grid voxel edge")
+    ap.add_argument("--train-large-grid", action="store_true",
+                    help="opt in to training on grids of side 12..32 (DeepVCP(train_large_grid=True))")
     args = ap.parse_args()
     if args.bn_train and not args.train_fe:
         ap.error("--bn-train needs --train-fe")
@@ -51,7 +58,7 @@ def main():
     from dvcp.synthetic import condition_weights, make_pairs, randomize_bn
     dev = torch.device("cuda", 0)
     torch.manual_seed(0)
-    model = dvcp.DeepVCP(use_normal=False, K=64, r=2.0, s=0.4).to(dev)
+    model = dvcp.DeepVCP(use_normal=False, K=64, r=args.r, s=args.s, train_large_grid=args.train_large_grid).to(dev)
     src, tgt, R_gt, t_gt = [t.to(dev) for t in make_pairs(args.batch, args.npoints, seed=1234)]
     randomize_bn(model)
     model.FE1.eval()
@@ -128,7 +135,8 @@ def main():
         "prefetch": P,
         "value": round(args.batch * args.steps / dt, 3), "unit": "pairs/s",
         "ms_per_step": round(1e3 * dt / args.steps, 3), "steps": args.steps, "warmup": args.warmup,
-        "config": {"pairs": args.batch, "n_points": args.npoints, "K": 64, "r": 2.0, "s": 0.4},
+        "config": {"pairs": args.batch, "n_points": args.npoints, "K": 64, "r": args.r, "s": args.s,
+                   "G": int((2 * args.r) / args.s + 1), "train_large_grid": args.train_large_grid},
         "loss_first_last": [float(losses[0].detach()), float(losses[-1].detach())],
         "stages": stages}))
 
