@@ -49,6 +49,7 @@ SIGNATURES = {
     "dvcp_knn": [_I, _P, _L, _L, _L, _I, _P, _L, _L, _L, _I, _I, _I, _P, _P, _P, _P],
     "dvcp_knn_tiled": [_I, _P, _L, _L, _L, _I, _P, _L, _L, _L, _I, _I, _I, _P, _P, _P, _P, _P],
     "dvcp_knn_tiled_insert": [_I, _P, _L, _L, _L, _I, _P, _L, _L, _L, _I, _I, _I, _P, _P, _P, _P, _P],
+    "dvcp_knn_slabs": [_I, _P, _L, _L, _L, _I, _P, _L, _L, _L, _I, _I, _I, _P, _P, _P, _P, _P],
     "dvcp_knn_tiled_order_probe": [_I, _P, _L, _L, _L, _I, _P, _L, _L, _L, _I, _I, _P, _P, _P, _P, _P, _P],
     "dvcp_dfe": [_I, _P, _L, _P, _P, _P],
     "dvcp_dfe_tgt": [_I, _P, _L, _L, _L, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P],
@@ -110,6 +111,8 @@ def load():
                            f"{ABI_VERSION}: rebuild it (make -j16 in deepvcp-pointcloud-registration_amd/)")
     lib.dvcp_knn_tiled_workspace_bytes.restype = ctypes.c_int64
     lib.dvcp_knn_tiled_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
+    lib.dvcp_knn_slabs_workspace_bytes.restype = ctypes.c_int64
+    lib.dvcp_knn_slabs_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]
     lib.dvcp_fps_workspace_bytes.restype = ctypes.c_int64
     lib.dvcp_fps_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int]
     lib.dvcp_fps_pair_workspace_bytes.restype = ctypes.c_int64
@@ -164,7 +167,7 @@ def load():
 
 def exported_symbols():
     return ["dvcp_last_error", "dvcp_abi_version",
-            "dvcp_knn_tiled_workspace_bytes", "dvcp_ball_query_workspace_bytes",
+            "dvcp_knn_tiled_workspace_bytes", "dvcp_knn_slabs_workspace_bytes", "dvcp_ball_query_workspace_bytes",
             "dvcp_sa_group_mlp_workspace_bytes", "dvcp_dfe_backward_workspace_bytes",
             "dvcp_dfe_tgt_backward_workspace_bytes",
             "dvcp_cpg_backward_workspace_bytes", "dvcp_sa_group_mlp_backward_workspace_bytes",

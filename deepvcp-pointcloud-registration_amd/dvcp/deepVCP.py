@@ -59,6 +59,10 @@ class DeepVCP(nn.Module):
         10 MB, but when the extractor trains the target-feature gradient takes 4 KiB of workspace
         per row, 2.4 GB per pair at G = 21, K = 64, beside the (B, K, C, 32) target rows, their
         gradient and the kNN tables kept for the backward.
+        ``fe_npoint``: points each set-abstraction layer keeps (the reference's literal 10000), up to
+        65536.  Above 16384 the key-point top-k streams its score row (dvcp_topk) and the kNN runs
+        over index slabs of the target's feature points (dvcp_knn_slabs), with the same results as
+        the one-pass kernels.  Above 65536 the top-k raises a RuntimeError that names the limit.
         ``feat_dtype``: storage of the target feature table the fused target stage gathers
         (torch.float16: BASELINE C5's "fp16 features", dvcp_dfe_tgt_f16; inference only -- the
         reference keeps fp32 features, so float16 is not reference precision).

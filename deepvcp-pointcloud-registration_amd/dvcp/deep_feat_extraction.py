@@ -23,7 +23,10 @@ def fe_config(use_normal=True, npoint=10000):
 
 
 class feat_extraction_layer(nn.Module):
-    """deep_feat_extraction.py:5-32.  forward(pts (B, C_in, N)) -> (xyz (B, S, 3), feat (B, S, 32))."""
+    """deep_feat_extraction.py:5-32.  forward(pts (B, C_in, N)) -> (xyz (B, S, 3), feat (B, S, 32)).
+    ``npoint`` up to 65536 (the FPS split select, the ball query and the set-abstraction tables
+    take that many points and centres); in DeepVCP the key-point top-k over the S scores raises a
+    RuntimeError naming that limit above it."""
 
     def __init__(self, use_normal=True, npoint=10000):
         super().__init__()

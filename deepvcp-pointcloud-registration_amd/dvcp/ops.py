@@ -347,16 +347,31 @@ def voxelize(pts, r, s, G, pdim=1):
 #          lane-private candidate buffers merged by bitonic networks); M <= KNN_TILED_MAX_M.
 #   tiled_insert: the same scan inserting every candidate into the sorted list at once (the
 #          round-2 kernel, dvcp_knn_tiled_insert), kept for parity tests and A/B timing.
+#   tiled_slabs: M above KNN_TILED_MAX_M (up to KNN_SLABS_MAX_M): the reference cut into index slabs
+#          of at most 16384 points, the tiled kernels once per slab, and a fold kernel merging each
+#          slab's k-list into a running list ordered by (d2, global index) (dvcp_knn_slabs).  Takes
+#          any M >= 1 when forced (one slab: the tiled call plus a fold).
 #   brute: index-order scan of every reference point (dvcp_knn); best for small M.
 # (A per-query cell-shell search over a uniform grid left the tree with ABI version 5: it lost on
 # the forward's workload, where most voxel candidates lie outside the target cloud --
 # profiles/round1: 35.8 ms vs 12.4 ms brute per C3 step.)
 KNN_TILED_MIN_M = 512
 KNN_TILED_MAX_M = 16384
+KNN_SLABS_MAX_M = 1 << 20
 
 
 def knn_method(M):
+    if KNN_TILED_MAX_M < M <= KNN_SLABS_MAX_M:
+        return "tiled_slabs"
     return "tiled" if KNN_TILED_MIN_M <= M <= KNN_TILED_MAX_M else "brute"
+
+
+def knn_slab_geometry(M):
+    """(slabs, points per slab) of dvcp_knn_slabs: ceil(M / 16384) slabs contiguous in index, each
+    round_up(ceil(M / slabs), 16) points, the last one shorter."""
+    n = max(1, (M + KNN_TILED_MAX_M - 1) // KNN_TILED_MAX_M)
+    per = (M + n - 1) // n
+    return n, (per + 15) // 16 * 16
 
 
 def knn(ref, qry, k, ref_pdim=1, qry_pdim=1, want_idx64=True, method=None):
@@ -377,11 +392,15 @@ def knn(ref, qry, k, ref_pdim=1, qry_pdim=1, want_idx64=True, method=None):
         ws = torch.empty(int(_lib.load().dvcp_knn_tiled_workspace_bytes(B, M, Q)), dtype=torch.uint8, device=dev)
         call("dvcp_knn_" + method, dtype_code(ref), ptr(ref), rb, rc, rn, M, ptr(qry), qb, qc, qn, Q, B, int(k), ptr(ws),
              ptr(dist), ptr(idx), ptr(idx64), stream(), work=work)
+    elif method == "tiled_slabs":
+        ws = torch.empty(int(_lib.load().dvcp_knn_slabs_workspace_bytes(B, M, Q, int(k))), dtype=torch.uint8, device=dev)
+        call("dvcp_knn_slabs", dtype_code(ref), ptr(ref), rb, rc, rn, M, ptr(qry), qb, qc, qn, Q, B, int(k), ptr(ws),
+             ptr(dist), ptr(idx), ptr(idx64), stream(), work=work)
     elif method == "brute":
         call("dvcp_knn", dtype_code(ref), ptr(ref), rb, rc, rn, M, ptr(qry), qb, qc, qn, Q, B, int(k), ptr(dist),
              ptr(idx), ptr(idx64), stream(), work=work)
     else:
-        raise ValueError(f"dvcp: unknown kNN method {method!r} (tiled, tiled_insert or brute)")
+        raise ValueError(f"dvcp: unknown kNN method {method!r} (tiled, tiled_insert, tiled_slabs or brute)")
     return dist, idx, idx64
 
 

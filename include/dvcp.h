@@ -197,7 +197,10 @@ int dvcp_fe_head_rows(const float* x, const int64_t* rows, int S, int Nx, int P,
 int dvcp_weighting(const float* feat, int P, const float* params, float* score, void* stream);
 
 /* Top-K per row (descending value, ties to the lower index).  Replaces
- * weighting_layer.py:31 torch.topk(X, K, dim=1).  score: B x S fp32 -> idx: B x K int64. */
+ * weighting_layer.py:31 torch.topk(X, K, dim=1).  score: B x S fp32 -> idx: B x K int64.
+ * S <= 65536 (above: an error naming the limit).  S <= 16384 keeps the row's keys in registers
+ * and takes any K <= S; 16384 < S <= 65536 streams the row from L2 in every radix pass and
+ * takes K <= 1024 (above: an error naming both limits). */
 int dvcp_topk(const float* score, int B, int S, int K, int64_t* idx, void* stream);
 
 /* Source key-point stage, one workgroup per pair.  Replaces deepVCP.py:44-68 +
@@ -247,6 +250,22 @@ int dvcp_knn_tiled_insert(int dtype, const void* ref, int64_t rb, int64_t rc, in
                           const void* qry, int64_t qb, int64_t qc, int64_t qn, int Q, int B, int k,
                           void* workspace, float* dist, int32_t* idx, int64_t* idx64, void* stream);
 int64_t dvcp_knn_tiled_workspace_bytes(int B, int M, int Q);
+/* Exact kNN for more reference points than dvcp_knn_tiled takes: same contract, arguments and
+ * results as dvcp_knn / dvcp_knn_tiled, 1 <= M <= 1048576, 1 <= k <= 32, finite inputs.  The
+ * reference is cut into S = ceil(M / 16384) slabs contiguous in index, each L = round_up(ceil(M /
+ * S), 16) points (the last shorter); dvcp_knn_tiled's kernels run once per slab and a fold kernel
+ * (one lane per query) merges each slab's sorted k-list into a running list of packed keys
+ * d2_bits << 32 | global index, d2 recomputed from the coordinates, so the (d2, index) order and
+ * the lower-index tie rule hold across slabs.  With M <= 16384 it is one tiled call plus a fold.
+ * workspace: dvcp_knn_slabs_workspace_bytes(B, M, Q, k) bytes of 16-byte aligned device memory =
+ * dvcp_knn_tiled_workspace_bytes(B, L, Q) + 4 B Q k (one slab's indices) + 8 B Q k (running keys)
+ * + 16 B M (the reference as fp32 (x, y, z, 0) rows), each part rounded up to 256 bytes: it does
+ * not grow with the slab count.  -1 on negative arguments or M above the limit.  (Added without an
+ * ABI version change: no existing entry point changed.) */
+int64_t dvcp_knn_slabs_workspace_bytes(int B, int M, int Q, int k);
+int dvcp_knn_slabs(int dtype, const void* ref, int64_t rb, int64_t rc, int64_t rn, int M,
+                   const void* qry, int64_t qb, int64_t qc, int64_t qn, int Q, int B, int k,
+                   void* workspace, float* dist, int32_t* idx, int64_t* idx64, void* stream);
 /* Test hook: the tile order that dvcp_knn_tiled's k = 17..32 kernel gives every wave of 64
  * curve-ordered queries (the same device code, written out instead of scanned).  With T = ceil(M / 16)
  * tiles and W = ceil(Q / 64) waves per cloud, row = cloud * W + wave:
