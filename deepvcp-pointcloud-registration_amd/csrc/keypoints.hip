@@ -161,7 +161,7 @@ extern "C" int dvcp_src_keypoints(int dtype, const void* fe_xyz, const float* fe
                                   void* stream) {
   DVCP_REQUIRE(fe_xyz && fe_feat && topk && kstart && R_init && keypts && src_cat && moved,
                "dvcp_src_keypoints: null pointer");
-  DVCP_REQUIRE(K > 0 && K <= dvcp::kKpMaxK && K <= S, "dvcp_src_keypoints: K=%d unsupported (1..256, <= S)", K);
+  DVCP_REQUIRE(K > 0 && K <= dvcp::kKpMaxK && K <= S, "dvcp_src_keypoints: K=%d unsupported (1..256, <= S; up to 1024 take dvcp_src_keypoints_ws)", K);
   DVCP_REQUIRE(nsample > 0 && nsample <= dvcp::kKpMaxNs, "dvcp_src_keypoints: nsample=%d unsupported", nsample);
   // With K < nsample the reference's slice (pointnet2_utils.py:103) yields K columns and its
   // DFE MaxPool1d(32) then rejects the input; keep that case an error here too.
@@ -186,7 +186,9 @@ extern "C" int dvcp_src_keypoints_backward(int dtype, const void* fe_xyz, int S,
                                            const int64_t* kstart, double radius, int nsample, const float* grad_cat,
                                            float* grad_feat, void* stream) {
   DVCP_REQUIRE(K > 0 && K <= dvcp::kKpMaxK && K <= S && nsample > 0 && nsample <= dvcp::kKpMaxNs && K >= nsample,
-               "dvcp_src_keypoints_backward: K=%d nsample=%d unsupported", K, nsample);
+               "dvcp_src_keypoints_backward: K=%d nsample=%d unsupported (K <= 256; up to 1024 take "
+               "dvcp_src_keypoints_backward_ws)",
+               K, nsample);
   if (B == 0) return DVCP_OK;
   DVCP_REQUIRE(fe_xyz && topk && kstart && grad_cat && grad_feat, "dvcp_src_keypoints_backward: null pointer");
   hipStream_t st = static_cast<hipStream_t>(stream);

@@ -45,6 +45,7 @@ SIGNATURES = {
     "dvcp_weighting": [_P, _I, _P, _P, _P],
     "dvcp_topk": [_P, _I, _I, _I, _P, _P],
     "dvcp_src_keypoints": [_I, _P, _P, _I, _P, _I, _I, _P, _D, _I, _P, _L, _P, _P, _P, _P],
+    "dvcp_src_keypoints_ws": [_I, _P, _P, _I, _P, _I, _I, _P, _D, _I, _P, _L, _P, _P, _P, _P, _L, _P],
     "dvcp_voxelize": [_I, _P, _L, _L, _L, _I, _I, _D, _D, _I, _P, _P, _P],
     "dvcp_knn": [_I, _P, _L, _L, _L, _I, _P, _L, _L, _L, _I, _I, _I, _P, _P, _P, _P],
     "dvcp_knn_tiled": [_I, _P, _L, _L, _L, _I, _P, _L, _L, _L, _I, _I, _I, _P, _P, _P, _P, _P],
@@ -73,6 +74,7 @@ SIGNATURES = {
     "dvcp_dfe_backward": [_I, _P, _L, _P, _P, _P, _P, _P, _P],
     "dvcp_dfe_tgt_backward": [_I, _P, _L, _L, _L, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P],
     "dvcp_src_keypoints_backward": [_I, _P, _I, _P, _I, _I, _P, _D, _I, _P, _P, _P],
+    "dvcp_src_keypoints_backward_ws": [_I, _P, _L, _I, _I, _I, _I, _P, _P, _P],
     "dvcp_cpg_backward": [_P, _P, _L, _L, _L, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P],
     "dvcp_cpg_tiled_backward": [_P, _P, _L, _L, _L, _P, _I, _I, _P, _P, _P, _P, _P, _L, _P, _P],
     "dvcp_sa_group_mlp_backward": [_I, _P, _L, _L, _L, _I, _P, _L, _L, _L, _I, _I, _I, _P, _L, _L, _L, _I,
@@ -145,6 +147,8 @@ def load():
     lib.dvcp_cpg_tiled_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int]
     lib.dvcp_cpg_tiled_backward_workspace_bytes.restype = ctypes.c_int64
     lib.dvcp_cpg_tiled_backward_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int]
+    lib.dvcp_src_keypoints_workspace_bytes.restype = ctypes.c_int64
+    lib.dvcp_src_keypoints_workspace_bytes.argtypes = [ctypes.c_int] * 4
     lib.dvcp_cpg1d_nparams.restype = ctypes.c_int
     lib.dvcp_cpg1d_nparams.argtypes = []
     lib.dvcp_sa_bn_pack_floats.restype = ctypes.c_int64
@@ -175,7 +179,7 @@ def exported_symbols():
             "dvcp_sa_bn_pack_floats", "dvcp_sa_bn_rows_floats", "dvcp_sa_bn_feat_workspace_bytes", "dvcp_sa_bn_zrows_floats",
             "dvcp_cpg1d_nparams", "dvcp_sa_bnm_supported", "dvcp_sa_bnm_workspace_bytes",
             "dvcp_fps_pair_workspace_bytes", "dvcp_fps_workspace_bytes", "dvcp_cpg_tiled_workspace_bytes",
-            "dvcp_cpg_tiled_backward_workspace_bytes"] + list(SIGNATURES)
+            "dvcp_cpg_tiled_backward_workspace_bytes", "dvcp_src_keypoints_workspace_bytes"] + list(SIGNATURES)
 
 
 # When a list, every entry-point call appends (name, start_event, end_event, work) recorded on

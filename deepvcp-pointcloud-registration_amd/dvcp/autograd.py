@@ -12,7 +12,8 @@ feature extractor.  Here the head's backward runs in hand-written HIP kernels:
   * ``dfe_tgt``    -- the fused target rows (dvcp_dfe_tgt / dvcp_dfe_tgt_backward), also
                       differentiable in the target features (the get_cat_feat_tgt.py:85 gather);
   * ``src_keypoints`` -- the key-point stage, differentiable in the source features (the
-                      pointnet2_utils.py:59 gather, dvcp_src_keypoints_backward).
+                      pointnet2_utils.py:59 gather, dvcp_src_keypoints_backward; above 256 key
+                      points dvcp_src_keypoints_backward_ws on the forward's workspace).
 
   * ``feat_extraction`` -- the feature extractor (deep_feat_extraction.py:18-32 + REF-R R1): fc
                       (dvcp_fe_head_backward) and the three set-abstraction MLPs, chained through the
@@ -104,20 +105,34 @@ class _Cpg(torch.autograd.Function):
 class _SrcKeypoints(torch.autograd.Function):
     @staticmethod
     def forward(ctx, fe_xyz, fe_feat, topk_idx, kstart, R_init, radius, nsample):
-        keypts, src_cat, moved = ops.src_keypoints(fe_xyz, fe_feat, topk_idx, kstart, R_init, radius=radius,
-                                                   nsample=nsample)
-        ctx.save_for_backward(fe_xyz, topk_idx, kstart)
+        ctx.method = ops.src_keypoints_method(topk_idx.shape[1])
         ctx.radius, ctx.nsample, ctx.feat_dtype = radius, nsample, fe_feat.dtype
+        if ctx.method == "split":
+            # K > 256 (dvcp_src_keypoints_ws): the backward reads the forward's workspace (FPS order,
+            # ball lists, key-point coordinates) instead of repeating the serial FPS
+            keypts, src_cat, moved, ws = ops.src_keypoints(fe_xyz, fe_feat, topk_idx, kstart, R_init, radius=radius,
+                                                           nsample=nsample, return_workspace=True)
+            ctx.save_for_backward(ws)
+            ctx.S, ctx.K, ctx.xyz_dtype = fe_xyz.shape[2], topk_idx.shape[1], fe_xyz.dtype
+        else:
+            keypts, src_cat, moved = ops.src_keypoints(fe_xyz, fe_feat, topk_idx, kstart, R_init, radius=radius,
+                                                       nsample=nsample)
+            ctx.save_for_backward(fe_xyz, topk_idx, kstart)
         ctx.mark_non_differentiable(keypts, moved)
         return keypts, src_cat, moved
 
     @staticmethod
     def backward(ctx, g_kp, g_cat, g_moved):
-        fe_xyz, topk_idx, kstart = ctx.saved_tensors
         gF = None
         if ctx.needs_input_grad[1] and g_cat is not None:
-            gF = ops.src_keypoints_backward(fe_xyz, topk_idx, kstart, g_cat, radius=ctx.radius,
-                                            nsample=ctx.nsample).to(ctx.feat_dtype)
+            if ctx.method == "split":
+                ws, = ctx.saved_tensors
+                gF = ops.src_keypoints_backward_ws(ws, ctx.S, ctx.K, g_cat, nsample=ctx.nsample,
+                                                   dtype=ctx.xyz_dtype).to(ctx.feat_dtype)
+            else:
+                fe_xyz, topk_idx, kstart = ctx.saved_tensors
+                gF = ops.src_keypoints_backward(fe_xyz, topk_idx, kstart, g_cat, radius=ctx.radius,
+                                                nsample=ctx.nsample).to(ctx.feat_dtype)
         return None, gF, None, None, None, None, None
 
 

@@ -46,7 +46,14 @@ def _warn_f16_autograd():
 class DeepVCP(nn.Module):
     def __init__(self, use_normal, K=64, r=1.0, s=0.4, fe_npoint=10000, feat_dtype=torch.float32, dfe_literal=False,
                  fps_parts=None, train_large_grid=False):
-        """``r``, ``s``: the candidate grid's search radius and voxel edge; its side
+        """``K``: key points per pair, up to 1024.  Up to 256 the key-point stage of a pair runs in
+        one workgroup's LDS (dvcp_src_keypoints); 257..1024 take the split stage (dvcp_src_keypoints_ws:
+        FPS, ball query and rows as separate launches over a workspace, same results).  1024 is where
+        the streamed top-k (dvcp_topk, fe_npoint > 16384) and the pose solve's inlier ranking
+        (dvcp_svd_optimization) stop; a forward with K > 1024 raises a ValueError that names the limit
+        before the extractor runs.  Every later stage is sized by B K C (the fused target rows'
+        backward needs B K C < 2^26 when the extractor trains).
+        ``r``, ``s``: the candidate grid's search radius and voxel edge; its side
         G = int(2r/s + 1) must be <= 32.  Grids above 11 take the tiled CPG (dvcp_cpg_tiled); they
         train with ``train_large_grid=True`` (backward: dvcp_cpg_tiled_backward).  Without it a
         forward that records autograd at G > 11 raises NotImplementedError, as before; the default
@@ -201,6 +208,7 @@ class DeepVCP(nn.Module):
         for parity testing -- use these FE-space key-point indices instead of the top-k.
         ``return_weights``: also return the key points' weighting-layer scores (B, K), the
         weights of the paper's weighted pose solve (dvcp.paper)."""
+        ops.src_keypoints_method(self.K)   # K above the key-point stage's limit: ValueError before any launch
         train_head, train_fe = self._training_mode()
         if train_head:
             # before any launch

@@ -305,11 +305,34 @@ def topk(score, K):
     return idx
 
 
-def src_keypoints(fe_xyz, fe_feat, topk_idx, kstart, R_init, radius=1.0, nsample=32):
-    """deepVCP.py:44-68 + get_cat_feat_src.py + deepVCP.py:86-91 (REF-R R2/R3)."""
+SRC_KEYPOINTS_LDS_MAX_K = 256   # dvcp_src_keypoints: the pair's whole stage in one workgroup's LDS (csrc/keypoints.hip)
+SRC_KEYPOINTS_MAX_K = 1024      # dvcp_src_keypoints_ws: split over launches and a workspace (csrc/keypoints_split.hip)
+
+
+def src_keypoints_method(K):
+    """The key-point stage a key-point count takes: "lds" (dvcp_src_keypoints) up to 256, "split"
+    (dvcp_src_keypoints_ws) for 257..1024; ValueError above."""
+    K = int(K)
+    if K > SRC_KEYPOINTS_MAX_K:
+        raise ValueError(f"src_keypoints: K={K} key points unsupported: the key-point stage, the streamed top-k and "
+                         f"the pose solve take K <= {SRC_KEYPOINTS_MAX_K}")
+    return "lds" if K <= SRC_KEYPOINTS_LDS_MAX_K else "split"
+
+
+def src_keypoints(fe_xyz, fe_feat, topk_idx, kstart, R_init, radius=1.0, nsample=32, method=None,
+                  return_workspace=False):
+    """deepVCP.py:44-68 + get_cat_feat_src.py + deepVCP.py:86-91 (REF-R R2/R3).
+    ``method``: None (``src_keypoints_method(K)``), "lds" (K <= 256) or "split" (any K <= 1024: tests,
+    A/B).  ``return_workspace``: also return the split path's workspace (a uint8 tensor holding the
+    key points' coordinates, FPS order and ball lists, which ``src_keypoints_backward_ws`` reads;
+    None for "lds")."""
+    K = topk_idx.shape[1]
+    auto = src_keypoints_method(K)   # before any allocation or launch
+    method = auto if method is None else method
+    if method not in ("lds", "split"):
+        raise ValueError(f"dvcp: unknown key-point method {method!r} (lds or split)")
     _lib.require_gpu(fe_xyz, fe_feat, topk_idx, kstart, R_init)
     B, _, S = fe_xyz.shape
-    K = topk_idx.shape[1]
     if R_init.dtype != torch.float64:
         # deepVCP.py:90 multiplies R_init with a .double() tensor; any other dtype raises there.
         raise RuntimeError(f"expected R_init of dtype torch.float64, got {R_init.dtype}")
@@ -325,8 +348,18 @@ def src_keypoints(fe_xyz, fe_feat, topk_idx, kstart, R_init, radius=1.0, nsample
     keypts = torch.empty(B, K, 3, dtype=fe_xyz.dtype, device=dev)
     src_cat = torch.empty(B, K, nsample, 35, dtype=torch.float32, device=dev)
     moved = torch.empty(B, K, 3, dtype=torch.float64, device=dev)
-    call("dvcp_src_keypoints", dtype_code(fe_xyz), ptr(xyz_c), ptr(feat_c), S, ptr(top_c), B, K, ptr(ks_c),
-         float(radius), int(nsample), ptr(R), r_b, ptr(keypts), ptr(src_cat), ptr(moved), stream())
+    ws = None
+    if method == "lds":
+        call("dvcp_src_keypoints", dtype_code(fe_xyz), ptr(xyz_c), ptr(feat_c), S, ptr(top_c), B, K, ptr(ks_c),
+             float(radius), int(nsample), ptr(R), r_b, ptr(keypts), ptr(src_cat), ptr(moved), stream())
+    else:
+        nbytes = int(_lib.load().dvcp_src_keypoints_workspace_bytes(dtype_code(fe_xyz), B, K, int(nsample)))
+        ws = torch.empty(max(16, nbytes), dtype=torch.uint8, device=dev)
+        call("dvcp_src_keypoints_ws", dtype_code(fe_xyz), ptr(xyz_c), ptr(feat_c), S, ptr(top_c), B, K,
+             ptr(ks_c), float(radius), int(nsample), ptr(R), r_b, ptr(keypts), ptr(src_cat), ptr(moved), ptr(ws),
+             ws.numel(), stream())
+    if return_workspace:
+        return keypts, src_cat, moved, ws
     return keypts, src_cat, moved
 
 
@@ -691,6 +724,23 @@ def src_keypoints_backward(fe_xyz, topk_idx, kstart, grad_cat, radius=1.0, nsamp
     gF = torch.zeros(B, S_, 32, dtype=torch.float32, device=dev)
     call("dvcp_src_keypoints_backward", dtype_code(fe_xyz), ptr(xyz_c), S_, ptr(top_c), B, K, ptr(ks_c),
          float(radius), int(nsample), ptr(g), ptr(gF), stream())
+    return gF
+
+
+def src_keypoints_backward_ws(ws, S, K, grad_cat, nsample=32, dtype=torch.float32):
+    """``src_keypoints_backward`` for the split path (dvcp_src_keypoints_backward_ws): ``ws`` is the
+    workspace ``src_keypoints(..., method="split", return_workspace=True)`` returned, ``S`` the FE
+    row count, ``dtype`` the coordinates' dtype of that forward.  Any K <= 1024."""
+    _lib.require_gpu(ws, grad_cat)
+    B = grad_cat.shape[0]
+    if tuple(grad_cat.shape) != (B, K, nsample, 35):
+        raise RuntimeError(f"src_keypoints_backward_ws: grad_cat must be (B, {K}, {nsample}, 35), "
+                           f"got {tuple(grad_cat.shape)}")
+    g = grad_cat.float().contiguous()
+    gF = torch.zeros(B, S, 32, dtype=torch.float32, device=g.device)
+    code = {torch.float32: _lib.F32, torch.float64: _lib.F64}[dtype]
+    call("dvcp_src_keypoints_backward_ws", code, ptr(ws), ws.numel() * ws.element_size(), int(S), B, int(K),
+         int(nsample), ptr(g), ptr(gF), stream())
     return gF
 
 

@@ -211,11 +211,30 @@ int dvcp_topk(const float* score, int B, int S, int K, int64_t* idx, void* strea
  * fe_xyz: B x 3 x S (dtype, channel-first), fe_feat: B x S x 32 fp32, topk: B x K int64,
  * R_init: B x 3 x 3 fp64 (row stride r_b: 0 broadcasts one matrix).
  * Outputs: keypts B x K x 3 (dtype), src_cat B x K x nsample x 35 fp32 (the DFE input after
- * its .float()), moved B x K x 3 fp64. */
+ * its .float()), moved B x K x 3 fp64.  K <= 256 (everything in one workgroup's LDS); up to 1024
+ * take dvcp_src_keypoints_ws. */
 int dvcp_src_keypoints(int dtype, const void* fe_xyz, const float* fe_feat, int S,
                        const int64_t* topk, int B, int K, const int64_t* kstart,
                        double radius, int nsample, const double* R_init, int64_t r_b,
                        void* keypts, float* src_cat, double* moved, void* stream);
+
+/* Source key-point stage for up to 1024 key points, split over several launches.  Replaces the same
+ * reference lines as dvcp_src_keypoints (deepVCP.py:44-68, get_cat_feat_src.py:16-55,
+ * deepVCP.py:86-91) with the same arguments, outputs and rounding, for 1 <= K <= 1024 (K <= S,
+ * nsample <= K, nsample <= 32): one workgroup per pair gathers the key points and runs the FPS
+ * among them (pointnet2_utils.py:63-84), one wave per centre the ball query (:87-107), eight key
+ * points per workgroup the rows of get_cat_feat_src.py:37-53.  Every K in that range takes this
+ * path (tests compare it with dvcp_src_keypoints at K <= 256).  fe_feat must be 16-byte aligned.
+ * workspace: dvcp_src_keypoints_workspace_bytes(dtype, B, K, nsample) bytes, 16-byte aligned (the
+ * size is a multiple of 16; 0 for arguments this entry refuses and for B <= 0).  After the call it
+ * holds the key points' coordinates (B x 3 x K, dtype), the FPS order (B x K int32) and the ball
+ * lists (B x K x nsample int32), which dvcp_src_keypoints_backward_ws reads.  B = 0 is a no-op. */
+int64_t dvcp_src_keypoints_workspace_bytes(int dtype, int B, int K, int nsample);
+int dvcp_src_keypoints_ws(int dtype, const void* fe_xyz, const float* fe_feat, int S,
+                          const int64_t* topk, int B, int K, const int64_t* kstart,
+                          double radius, int nsample, const double* R_init, int64_t r_b,
+                          void* keypts, float* src_cat, double* moved, void* workspace,
+                          int64_t ws_bytes, void* stream);
 
 /* Candidate grid.  Replaces voxelize.py:19-83: cand[b,k,(ix*G+iy)*G+iz,a] =
  * fp32(fma(s, i_a, (c_a - r) - s/2)) evaluated in fp64 (torch.arange, Q9).
@@ -616,6 +635,13 @@ int dvcp_dfe_tgt_backward(int dtype, const void* ref_xyz, int64_t rb, int64_t rc
 int dvcp_src_keypoints_backward(int dtype, const void* fe_xyz, int S, const int64_t* topk, int B, int K,
                                 const int64_t* kstart, double radius, int nsample, const float* grad_cat,
                                 float* grad_feat, void* stream);
+/* The same for dvcp_src_keypoints_ws (autograd through pointnet2_utils.py:59 and
+ * get_cat_feat_src.py:50): reads the workspace that forward left (same dtype, B, K, nsample; indices
+ * read from it are clamped to [0, K-1]) instead of repeating the FPS and the ball query.  grad_cat
+ * B x K x nsample x 35 -> grad_feat B x S x 32 fp32, accumulated with float atomics: zero it first;
+ * rows >= K stay untouched (Q4). */
+int dvcp_src_keypoints_backward_ws(int dtype, const void* workspace, int64_t ws_bytes, int S, int B, int K,
+                                   int nsample, const float* grad_cat, float* grad_feat, void* stream);
 
 /* CPG backward.  Replaces autograd through cpg.py:27-60: dvcp_cpg's arguments plus grad_vcp
  * (P x 3) -> grad_src (P x 32), grad_tgt (P x 32 x C contiguous, the (B,K,32,C) tensor's
