@@ -22,8 +22,15 @@ feature extractor.  Here the head's backward runs in hand-written HIP kernels:
                       (batch statistics, model.train() as train.py does): dvcp_sa_bn_backward
                       (dvcp/batchnorm.py).
 
+Paper mode (dvcp/paper.py, not reference parity) adds the two links its stage heads need:
+
+  * ``cpg1d``      -- the second stage's 1-D CPG (dvcp_cpg1d / dvcp_cpg1d_backward);
+  * ``weighting``  -- the paper's weighting layer (dvcp_weighting / dvcp_weighting_backward), whose
+                      scores are the pose solve's weights there and so do carry a gradient.
+
 The key points, candidates and kNN indices carry no gradient in the reference either (index
-ops, knn_cuda under no_grad); the weighting layer gets none (only its top-k indices are used).
+ops, knn_cuda under no_grad); the reference path's weighting layer gets none (only its top-k
+indices are used).
 Parameter gradients come back summed over
 the batch in a fixed order (deterministic); the feature scatters use float atomics.
 """
@@ -100,6 +107,42 @@ class _Cpg(torch.autograd.Function):
         gsrc = gsrc.view(src.shape).to(src.dtype) if ctx.needs_input_grad[0] else None
         gtgt = gtgt.to(tgt.dtype) if ctx.needs_input_grad[1] else None
         return (gsrc, gtgt, None, None, *_split(gp, ctx.weights))
+
+
+class _Cpg1d(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, src, tgt, cand, *weights):
+        params = _pack(weights)
+        ctx.save_for_backward(src, tgt, cand, params)
+        ctx.weights = [(w.shape, w.dtype) for w in weights]
+        return ops.cpg1d(src, tgt, cand, params)
+
+    @staticmethod
+    def backward(ctx, g):
+        src, tgt, cand, params = ctx.saved_tensors
+        want_src, want_tgt = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        gsrc, gtgt, gp = ops.cpg1d_backward(src, tgt, cand, params, g, want_src=want_src, want_tgt=want_tgt)
+        gsrc = gsrc.view(src.shape).to(src.dtype) if want_src else None
+        gtgt = gtgt.to(tgt.dtype) if want_tgt else None
+        return (gsrc, gtgt, None, *_split(gp, ctx.weights))
+
+
+class _Weighting(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, feat, folded):
+        rows = feat.contiguous().float()
+        params = folded.detach().float().contiguous()
+        ctx.save_for_backward(rows, params)
+        ctx.dtypes = (feat.dtype, folded.dtype)
+        return ops.weighting(rows, params)
+
+    @staticmethod
+    def backward(ctx, g):
+        rows, params = ctx.saved_tensors
+        want_feat = ctx.needs_input_grad[0]
+        gp, gfeat = ops.weighting_backward(rows, params, g, want_feat=want_feat)
+        return (gfeat.to(ctx.dtypes[0]) if want_feat else None,
+                gp.to(ctx.dtypes[1]) if ctx.needs_input_grad[1] else None)
 
 
 class _SrcKeypoints(torch.autograd.Function):
@@ -262,6 +305,22 @@ def cpg(src, tgt, cand, G, cpg_module, large_grid=False):
     require_trainable_grid(G, large_grid)
     convs = [cpg_module.conv1, cpg_module.conv2, cpg_module.conv3]
     return _Cpg.apply(src, tgt, cand, G, *[t for c in convs for t in (c.weight, c.bias)])
+
+
+def cpg1d(src, tgt, cand, cpg1d_module):
+    """The paper's 1-D CPG (Sec. 3.6; dvcp_cpg1d / dvcp_cpg1d_backward), differentiable in src
+    (B, K, 32), tgt (B, K, Gz, 32) and the three Conv1d layers of ``cpg1d_module`` (dvcp.paper.CPG1D)."""
+    convs = [cpg1d_module.conv1, cpg1d_module.conv2, cpg1d_module.conv3]
+    return _Cpg1d.apply(src, tgt, cand, *[t for c in convs for t in (c.weight, c.bias)])
+
+
+def weighting(feat, weighting_module):
+    """The paper's weighting layer (Sec. 3.2; dvcp_weighting / dvcp_weighting_backward) on rows
+    (P, 32), differentiable in the rows and in ``weighting_module``'s (dvcp.paper.PaperWeighting)
+    fc1-3 and bn1-2 weights and biases: the eval-mode BN is folded into the linear layers by torch ops
+    recorded here (no cache), so torch carries the packed gradient back to them.  The running
+    statistics get no gradient and are not updated."""
+    return _Weighting.apply(feat, weighting_module.folded_params())
 
 
 def src_keypoints(fe_xyz, fe_feat, topk_idx, kstart, R_init, radius=1.0, nsample=32):

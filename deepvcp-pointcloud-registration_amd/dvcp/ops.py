@@ -1153,6 +1153,59 @@ def cpg1d(src, tgt, cand, params, want_weight=False):
     return (vcp, w) if want_weight else vcp
 
 
+CPG1D_MAX_GZ = 64       # dvcp_cpg1d / dvcp_cpg1d_backward: the z line of one wave
+WEIGHTING_NPARAMS = 32 * 16 + 16 + 16 * 8 + 8 + 8 + 1   # PaperWeighting.packed_params()
+
+
+def _workspace(nbytes, device):
+    return torch.empty(max(1, (int(nbytes) + 3) // 4), dtype=torch.float32, device=device)
+
+
+def cpg1d_backward(src, tgt, cand, params, grad_vcp, want_src=True, want_tgt=True):
+    """Gradients of ``cpg1d`` (paper Sec. 3.6): (d src (B, K, 32) or None, d tgt (B, K, Gz, 32) or None,
+    d params (dvcp_cpg1d_nparams())), the parameter gradient summed in a fixed order."""
+    _lib.require_gpu(src, tgt, cand, params, grad_vcp)
+    B, K, Gz, _ = cand.shape
+    if tuple(tgt.shape) != (B, K, Gz, 32) or src.numel() != B * K * 32 or grad_vcp.numel() != B * K * 3:
+        raise RuntimeError(f"cpg1d_backward: expected src (B, K, 32), tgt (B, K, Gz, 32), grad_vcp (B, K, 3) for "
+                           f"cand {tuple(cand.shape)}, got {tuple(src.shape)}, {tuple(tgt.shape)}, "
+                           f"{tuple(grad_vcp.shape)}")
+    P = B * K
+    dev = cand.device
+    s, t, c = src.reshape(P, 32).float().contiguous(), tgt.float().contiguous(), cand.float().contiguous()
+    gv = grad_vcp.reshape(P, 3).float().contiguous()
+    gsrc = torch.empty(B, K, 32, dtype=torch.float32, device=dev) if want_src else None
+    gtgt = torch.empty(B, K, Gz, 32, dtype=torch.float32, device=dev) if want_tgt else None
+    gp = torch.empty(int(_lib.load().dvcp_cpg1d_nparams()), dtype=torch.float32, device=dev)
+    ws = _workspace(_lib.load().dvcp_cpg1d_backward_workspace_bytes(P), dev)
+    macs = 3 * (32 * 16 + 16 * 4 + 4) * P * Gz
+    call("dvcp_cpg1d_backward", ptr(s), ptr(t), ptr(c), P, Gz, ptr(params), ptr(gv), ptr(gsrc), ptr(gtgt), ptr(ws),
+         ws.numel() * 4, ptr(gp), stream(),
+         work=(2.0 * macs * (3 if (want_src or want_tgt) else 2), 4.0 * P * (32 + Gz * (35 + 32) + 6)))
+    return gsrc, gtgt, gp
+
+
+def weighting_backward(feat, params, grad_score, want_feat=True):
+    """Gradients of ``weighting`` (paper Sec. 3.2) on the folded parameters: (d params
+    (WEIGHTING_NPARAMS, the forward's layout, summed in a fixed order), d feat (P, 32) or None)."""
+    _lib.require_gpu(feat, params, grad_score)
+    if feat.dim() != 2 or feat.shape[1] != 32 or feat.dtype != torch.float32 or not feat.is_contiguous():
+        raise RuntimeError(f"weighting_backward: feat must be contiguous (P, 32) fp32, got {tuple(feat.shape)}")
+    P = feat.shape[0]
+    if params.numel() != WEIGHTING_NPARAMS or grad_score.numel() != P:
+        raise RuntimeError(f"weighting_backward: expected {WEIGHTING_NPARAMS} parameters and {P} score gradients, got "
+                           f"{params.numel()} and {grad_score.numel()}")
+    dev = feat.device
+    g = grad_score.reshape(P).float().contiguous()
+    gfeat = torch.empty(P, 32, dtype=torch.float32, device=dev) if want_feat else None
+    gp = torch.empty(WEIGHTING_NPARAMS, dtype=torch.float32, device=dev)
+    ws = _workspace(_lib.load().dvcp_weighting_backward_workspace_bytes(P), dev)
+    macs = (32 * 16 + 16 * 8 + 8) * P
+    call("dvcp_weighting_backward", ptr(feat), P, ptr(params), ptr(g), ptr(gfeat), ptr(ws), ws.numel() * 4, ptr(gp),
+         stream(), work=(2.0 * macs * (3 if want_feat else 2), 4.0 * P * (32 + 1 + (32 if want_feat else 0))))
+    return gp, gfeat
+
+
 def paper_pose(x, y, w, reflection_fix=True, inlier_ratio=1.0, R_true=None, t_true=None):
     """Weighted Kabsch with reflection fix and the paper's outlier rejection on (B, 3, n) fp64
     operands (w (B, n) or None) -> R (B, 3, 3), t (B, 3, 1)[, partial (B, 2) with R_true, t_true]."""

@@ -16,13 +16,15 @@ choices the paper leaves open.
     then a 32-unit fully connected layer (fused into the last propagation launch).
   * ``DeepVCPPaper`` -- the whole network with duplication (Sec. 3.6): a shared feature extractor
     and two cascaded stages, the second fed with the first's pose and generating candidates on a
-    z line scored by a 1-D CNN (dvcp_cpg1d).  Inference (eval, no_grad).
+    z line scored by a 1-D CNN (dvcp_cpg1d).  Inference by default; ``train_heads=True`` trains
+    the two stages' heads (weighting layer, DFE, CPG) with the extractor frozen.
 """
 import torch
 import torch.nn as nn
 
-from . import _lib, ops
+from . import _lib, autograd, ops
 from ._params import bn_affine, cached_pack
+from .cpg import _wants_grad
 from .cpg import cpg as _cpg3d
 from .deep_feat_embedding import feat_embedding_layer
 from .pointnet2_utils import PointNetSetAbstraction, _inference_only
@@ -178,7 +180,10 @@ class PaperFeatExtraction(nn.Module):
 
 class PaperWeighting(nn.Module):
     """Paper Sec. 3.2: FC 16 (BN, ReLU), FC 8 (BN, ReLU), FC 1 softplus; eval BN folded into the
-    linear layers, one HIP launch (dvcp_weighting)."""
+    linear layers, one HIP launch (dvcp_weighting).  In eval mode with autograd on and a parameter or
+    the input requiring a gradient, the scores carry one (backward: dvcp_weighting_backward, the fold
+    differentiated by torch down to fc1-3 and bn1-2's weight / bias; running statistics are fixed).
+    Training mode (batch-statistics BN) is refused."""
 
     def __init__(self):
         super().__init__()
@@ -190,25 +195,32 @@ class PaperWeighting(nn.Module):
         tensors = [self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias, self.fc3.weight, self.fc3.bias]
         tensors += [t for bn in (self.bn1, self.bn2) for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var)]
 
-        def build():
-            parts = []
-            for lin, bn in ((self.fc1, self.bn1), (self.fc2, self.bn2)):
-                s, h = bn_affine(bn)
-                parts += [(lin.weight * s[:, None]).reshape(-1), lin.bias * s + h]
-            return torch.cat(parts + [self.fc3.weight.reshape(-1), self.fc3.bias])
+        return cached_pack(self, "pwl", tensors, self.folded_params)
 
-        return cached_pack(self, "pwl", tensors, build)
+    def folded_params(self):
+        """W1 s1 | b1 s1 + h1 | W2 s2 | b2 s2 + h2 | W3 | b3 (s, h: the eval-mode BN as scale and shift),
+        plain torch ops: differentiable in the parameters when autograd records them (the training
+        path, uncached); ``packed_params`` caches the same values for inference."""
+        parts = []
+        for lin, bn in ((self.fc1, self.bn1), (self.fc2, self.bn2)):
+            s, h = bn_affine(bn)
+            parts += [(lin.weight * s[:, None]).reshape(-1), lin.bias * s + h]
+        return torch.cat(parts + [self.fc3.weight.reshape(-1), self.fc3.bias])
 
     def forward(self, f):
         """(B, N, 32) -> (B, N) scores."""
         _inference_only(self)
         B, N, _ = f.shape
+        if _wants_grad(self, f):
+            return autograd.weighting(f.reshape(B * N, 32), self).view(B, N)
         return ops.weighting(f.reshape(B * N, 32).contiguous().float(), self.packed_params()).view(B, N)
 
 
 class CPG1D(nn.Module):
     """Paper Sec. 3.6: the back network's CPG, Conv1d 32-16-4-1 (k 3, p 1) over a z line of
-    candidates, softmax, weighted candidate mean (one wave per key point, dvcp_cpg1d)."""
+    candidates, softmax, weighted candidate mean (one wave per key point, dvcp_cpg1d).  In eval mode
+    with autograd on and a parameter or an input requiring a gradient, the output carries one
+    (backward: dvcp_cpg1d_backward)."""
 
     def __init__(self):
         super().__init__()
@@ -222,6 +234,8 @@ class CPG1D(nn.Module):
 
     def forward(self, src, tgt, cand):
         _inference_only(self)
+        if _wants_grad(self, src, tgt):
+            return autograd.cpg1d(src, tgt, cand, self)
         return ops.cpg1d(src, tgt, cand, self.packed_params())
 
 
@@ -244,11 +258,28 @@ class DeepVCPPaper(nn.Module):
     checker; same submodule names and state_dict keys).  forward(src (B, C, N), tgt, R_init
     (B|1, 3, 3), t_init (B|1, 3[, 1])) -> list of per-stage dicts (keypts, vcp, weights, R, t, ...).
     ``starts``: (2, 3, B) FPS starts of the two FE calls; ``keypoint_idx``: optional per-stage
-    (B, K) key-point overrides for stage-decoupled parity tests."""
+    (B, K) key-point overrides for stage-decoupled parity tests.
+
+    ``train_heads`` (a plain attribute: no parameter or buffer, the state_dict is the same either
+    way).  False: inference, whether or not autograd is on (nothing returned carries a gradient).
+    True, in eval mode with autograd on: the two stages' heads train with the extractor frozen.
+    FE and the full-cloud scores run under no_grad and give the top-k; the K selected rows' scores
+    are recomputed differentiably (the layer is per row, so they are the gathered scores bit for
+    bit, and the weighting backward runs on B K rows instead of B N); the source and target DFE rows
+    go through ``autograd.dfe_rows``, the 3-D stage through ``autograd.cpg`` (the inference path's
+    (B, K, 32, C) view; grids above 11^3 as ``autograd.require_trainable_grid`` rules) and the
+    second stage through ``autograd.cpg1d``.  Stage 1's pose feeds stage 2 detached.  Each stage's
+    ``vcp`` and ``weights`` carry a gradient; the caller sums ``deepVCP_loss_paper`` over the stages.
+    A trainable FE parameter is refused (NotImplementedError) before any launch, and BatchNorm stays
+    in eval mode (``.train()`` is refused as before).
+    Memory: the materialised target rows (B, K C, 32, 35) fp32 are saved for backward: 4 * 32 * 35 *
+    K * C bytes per pair, about 381 MB at K = 64, C = 1331 (computed, not measured); fusing them as the
+    reference path's dvcp_dfe_tgt does is a later step."""
 
     def __init__(self, use_normal=False, K=64, r=2.0, s=0.4, s_z=0.25, d=1.0, nsample=32, duplication=True,
-                 inlier_ratio=0.8, **fe_cfg):
+                 inlier_ratio=0.8, train_heads=False, **fe_cfg):
         super().__init__()
+        self.train_heads = bool(train_heads)
         self.FE = PaperFeatExtraction(use_normal, **fe_cfg)
         self.stages = nn.ModuleList([_Stage(False)] + ([_Stage(True)] if duplication else []))
         self.K, self.r, self.s, self.s_z, self.d, self.ns = K, r, s, s_z, d, nsample
@@ -256,26 +287,42 @@ class DeepVCPPaper(nn.Module):
 
     def forward(self, src, tgt, R_init, t_init, starts=None, keypoint_idx=None):
         _inference_only(self)
+        train = self.train_heads and torch.is_grad_enabled()
+        if train:
+            if any(p.requires_grad for p in self.FE.parameters()):
+                raise NotImplementedError("dvcp: DeepVCPPaper(train_heads=True) trains the stage heads only: the "
+                                          "extractor must be frozen (model.FE.requires_grad_(False))")
+            autograd.require_trainable_grid(int(2 * self.r / self.s + 1), self.stages[0].cpg.train_large_grid)
         _lib.require_gpu(src, tgt)
+        with torch.enable_grad() if train else torch.no_grad():
+            return self._stages(src, tgt, R_init, t_init, starts, keypoint_idx, train)
+
+    def _stages(self, src, tgt, R_init, t_init, starts, keypoint_idx, train):
         B, _, N = src.shape
         dev = src.device
         if starts is None:
             starts = torch.stack([self.FE.draw_starts(B, N), self.FE.draw_starts(B, tgt.shape[2])])
-        f_src, f_tgt = self.FE(src, starts[0]), self.FE(tgt, starts[1])
+        with torch.no_grad():
+            f_src, f_tgt = self.FE(src, starts[0]), self.FE(tgt, starts[1])
         xs, xt = src[:, :3, :], tgt[:, :3, :]
         xs_rows = xs.permute(0, 2, 1)
         Rc = R_init.to(dev, torch.float64).expand(B, 3, 3)
         tc = t_init.to(dev, torch.float64).reshape(-1, 3).expand(B, 3)
         out = []
         for si, st in enumerate(self.stages):
-            score = st.WL(f_src)
+            with torch.no_grad():
+                score = st.WL(f_src)
             top = ops.topk(score, self.K) if keypoint_idx is None else keypoint_idx[si].to(dev, torch.int64)
-            w = torch.gather(score, 1, top)
+            if train:   # the K selected rows again, recorded: the gathered scores bit for bit
+                w = st.WL(torch.gather(f_src, 1, top[..., None].expand(B, self.K, 32)))
+            else:
+                w = torch.gather(score, 1, top)
             kp = torch.gather(xs_rows, 1, top[..., None].expand(B, self.K, 3)).contiguous()   # (B, K, 3)
             ns_src = min(self.ns, N)
             cnt, lst, _ = ops.ball_query(xs, kp, self.d, ns_src, pdim=2, cdim_pts=1)
             rows = ops.group_rows(kp, xs, f_src, cnt, lst, self.ns, self.d)
-            src_dfe = ops.dfe(rows, st.DFE.packed_params())                                  # (B, K, 32)
+            dfe = (lambda X: autograd.dfe_rows(X, st.DFE)) if train else (lambda X: ops.dfe(X, st.DFE.packed_params()))
+            src_dfe = dfe(rows)                                                              # (B, K, 32)
             moved = torch.einsum("bij,bkj->bki", Rc, kp.double()) + tc[:, None, :]
             if st.one_d:
                 G = int(2 * self.r / self.s_z + 1)
@@ -290,15 +337,21 @@ class DeepVCPPaper(nn.Module):
             ns_tgt = min(self.ns, xt.shape[2])
             cnt, lst, _ = ops.ball_query(xt, qry, self.d, ns_tgt, pdim=2, cdim_pts=1)
             trows = ops.group_rows(qry, xt, f_tgt, cnt, lst, self.ns, self.d)
-            tgt_dfe = ops.dfe(trows, st.DFE.packed_params()).view(B, self.K, C, 32)
+            tgt_dfe = dfe(trows).view(B, self.K, C, 32)    # train: trows (B, K C, 32, 35) saved for backward
+            # 3-D: cpg.py:34's reshape of a (B, K, 32, C) view whose row-major order is the
+            # candidates' own: the 3-D grid without the reference's Q11 scramble
             if st.one_d:
-                vcp = ops.cpg1d(src_dfe, tgt_dfe, cand, st.cpg.packed_params())
+                vcp = (autograd.cpg1d(src_dfe, tgt_dfe, cand, st.cpg) if train
+                       else ops.cpg1d(src_dfe, tgt_dfe, cand, st.cpg.packed_params()))
+            elif train:
+                vcp = autograd.cpg(src_dfe, tgt_dfe.contiguous().view(B, self.K, 32, C), cand, G, st.cpg,
+                                   large_grid=st.cpg.train_large_grid)
             else:
-                # cpg.py:34's reshape of a (B, K, 32, C) view whose row-major order is the
-                # candidates' own: the 3-D grid without the reference's Q11 scramble
                 vcp = ops.cpg(src_dfe, tgt_dfe.contiguous().view(B, self.K, 32, C), cand, G,
                               st.cpg.packed_params())
-            R, t = ops.paper_pose(kp.permute(0, 2, 1), vcp.permute(0, 2, 1), w, True, self.inlier_ratio)
+            # the pose carries no gradient (stage 2 starts from it detached, as the checker's numpy solve)
+            R, t = ops.paper_pose(kp.permute(0, 2, 1), vcp.detach().permute(0, 2, 1), w.detach(), True,
+                                  self.inlier_ratio)
             Rc, tc = R, t.reshape(B, 3)
             out.append(dict(keypts=kp, vcp=vcp, weights=w, R=R, t=t, topk=top, cand=cand, src_dfe=src_dfe,
                             tgt_dfe=tgt_dfe, score=score))

@@ -519,6 +519,34 @@ int dvcp_group_rows(const float* ctr, int64_t cb, int64_t cc, int64_t cn, int Q,
 int dvcp_cpg1d(const float* src, const float* tgt, const float* cand, int P, int Gz, const float* params,
                float* vcp, float* weight, void* stream);
 int dvcp_cpg1d_nparams(void);
+/* Backward of dvcp_cpg1d (paper Sec. 3.6; training of the duplicated network's head): the forward is
+ * recomputed per key point (one wave, the line in LDS, the row maximum subtracted in the softmax),
+ * then the weighted mean, the softmax and the three convolutions are differentiated.
+ * src, tgt, cand, P, Gz (1..64), params: as dvcp_cpg1d; grad_vcp: P x 3 fp32 (d loss / d vcp).
+ * grad_src (optional): P x 32; grad_tgt (optional): P x Gz x 32 (one writer per element);
+ * grad_params: dvcp_cpg1d_nparams() floats in the layout of params, summed over the key points in
+ * a fixed order (per-workgroup partial rows in workspace, folded in index order in fp64): two
+ * identical calls give identical bits.  workspace: ws_bytes >=
+ * dvcp_cpg1d_backward_workspace_bytes(P) bytes (0 for P <= 0).  P = 0: grad_params is zeroed and
+ * nothing else is read or written. */
+int64_t dvcp_cpg1d_backward_workspace_bytes(int P);
+int dvcp_cpg1d_backward(const float* src, const float* tgt, const float* cand, int P, int Gz,
+                        const float* params, const float* grad_vcp, float* grad_src, float* grad_tgt,
+                        void* workspace, int64_t ws_bytes, float* grad_params, void* stream);
+/* Backward of dvcp_weighting (paper Sec. 3.2: FC 32-16, ReLU, FC 16-8, ReLU, FC 8-1, softplus, on
+ * parameters with the eval-mode batch norm folded in by the caller; the kernel knows no BN).
+ * feat: P x 32 fp32; params: W1 (16 x 32) | b1 | W2 (8 x 16) | b2 | W3 (8) | b3 (673 floats, the
+ * forward's layout); grad_score: P fp32 (d loss / d score).  The forward is recomputed with the
+ * forward's own arithmetic, so the ReLU masks are the forward's; softplus' derivative is the
+ * logistic of the pre-activation, 1 where the forward takes its v > 20 branch.
+ * grad_feat (optional): P x 32; grad_params: 673 floats in the layout of params, summed over the
+ * rows in a fixed order (per-workgroup partial rows in workspace, folded in index order in fp64).
+ * workspace: ws_bytes >= dvcp_weighting_backward_workspace_bytes(P) bytes (0 for P <= 0).  P = 0:
+ * grad_params is zeroed. */
+int64_t dvcp_weighting_backward_workspace_bytes(int P);
+int dvcp_weighting_backward(const float* feat, int P, const float* params, const float* grad_score,
+                            float* grad_feat, void* workspace, int64_t ws_bytes, float* grad_params,
+                            void* stream);
 
 /* Corresponding point generation.  Replaces cpg.py:27-60: cost volume
  * (src - scrambled tgt)^2 (Q11), Conv3d 32-16-4-1 (k3, p1, no activations), softmax over C,
