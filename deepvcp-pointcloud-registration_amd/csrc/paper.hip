@@ -16,46 +16,12 @@
 //                    cpg.py:45-47), softmax over the line and the weighted candidate mean
 //                    (cpg.py:53-58).
 #include "common.h"
+#include "fp_common.h"
 
 namespace dvcp {
 
 // ------------------------------------------------------------------------ feature propagation
-constexpr int kFpRows = 32;      // points per workgroup
-constexpr int kFpThreads = 256;  // 8 threads per point in the 3-NN scan
-constexpr int kFpTile = 1024;    // xyz2 points per LDS tile
-constexpr int kFpMaxC = 128;     // widest row / layer input
-constexpr int kFpMaxCo = 64;     // widest layer output
-constexpr int kFpMaxL = 4;
-
-struct FpLayers {
-  int L;
-  int ch[kFpMaxL + 1];
-  int relu[kFpMaxL];
-};
-
-__device__ __forceinline__ uint64_t fp_key(float d2, int idx) {
-  return (static_cast<uint64_t>(float_order(d2)) << 32) | static_cast<uint32_t>(idx);
-}
-__device__ __forceinline__ float fp_key_d2(uint64_t k) {  // inverse of float_order
-  const uint32_t u = static_cast<uint32_t>(k >> 32);
-  return __uint_as_float((u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u);
-}
-__device__ __forceinline__ void top3_insert(uint64_t (&k)[3], uint64_t v) {
-  if (v < k[2]) {
-    if (v < k[1]) {
-      k[2] = k[1];
-      if (v < k[0]) {
-        k[1] = k[0];
-        k[0] = v;
-      } else {
-        k[1] = v;
-      }
-    } else {
-      k[2] = v;
-    }
-  }
-}
-
+// tile geometry, FpLayers and the 3-NN keys: fp_common.h (shared with the backward)
 __global__ __launch_bounds__(kFpThreads) void fp_kernel(PointsView<float> xyz1, int N1, PointsView<float> xyz2, int N2,
                                                         const float* __restrict__ p1, int64_t p1b, int64_t p1d,
                                                         int64_t p1n, int D1, const float* __restrict__ p2, int64_t p2b,

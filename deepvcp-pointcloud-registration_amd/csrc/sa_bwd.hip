@@ -461,6 +461,9 @@ extern "C" int dvcp_sa_group_mlp_backward(int dtype, const void* xyz, int64_t sb
   DVCP_SB(3, 16, 16, 32)
   DVCP_SB(32, 32, 64, 0)
   DVCP_SB(64, 64, 64, 0)
+  // the paper extractor's sa1 (dvcp/paper.py paper_fe_config), without / with normals
+  DVCP_SB(0, 32, 32, 0)
+  DVCP_SB(3, 32, 32, 0)
 #undef DVCP_SB
   dvcp::set_error("dvcp_sa_group_mlp_backward: unsupported table D=%d chans=%d,%d%s", D, chans[1], chans[2],
                   nlayer == 3 ? ",..." : "");

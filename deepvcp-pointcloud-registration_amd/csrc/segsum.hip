@@ -54,8 +54,8 @@ constexpr int kSegChunk = 64;
 template <int NC>
 __global__ __launch_bounds__(256) void seg_sum_kernel(const int* __restrict__ lo, const int* __restrict__ hi,
                                                       const uint32_t* __restrict__ vals,
-                                                      const float* __restrict__ contrib, int64_t nrows,
-                                                      float* __restrict__ out) {
+                                                      const float* __restrict__ contrib, int64_t stride,
+                                                      int64_t offset, int64_t nrows, float* __restrict__ out) {
   const int lane = threadIdx.x & 63;
   const int64_t row = static_cast<int64_t>(blockIdx.x) * 4 + (threadIdx.x >> 6);
   if (row >= nrows) return;  // wave-uniform
@@ -71,7 +71,7 @@ __global__ __launch_bounds__(256) void seg_sum_kernel(const int* __restrict__ lo
       for (int e = 0; e < kSegChunk / 2; ++e) {
         const uint32_t ve = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(vl), 2 * e));
         const uint32_t vo = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(vl), 2 * e + 1));
-        a[e] = 2 * e + h < n ? contrib[static_cast<int64_t>(h ? vo : ve) * 32 + c] : 0.f;
+        a[e] = 2 * e + h < n ? contrib[static_cast<int64_t>(h ? vo : ve) * stride + offset + c] : 0.f;
       }
 #pragma unroll
       for (int e = 0; e < kSegChunk / 2; ++e)
@@ -90,7 +90,7 @@ __global__ __launch_bounds__(256) void seg_sum_kernel(const int* __restrict__ lo
 #pragma unroll
         for (int e = 0; e < 32; ++e) {
           const uint32_t v = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(vl), e0 + e));
-          a[e] = e0 + e < n ? contrib[static_cast<int64_t>(v) * 64 + lane] : 0.f;
+          a[e] = e0 + e < n ? contrib[static_cast<int64_t>(v) * stride + offset + lane] : 0.f;
         }
 #pragma unroll
         for (int e = 0; e < 32; ++e)
@@ -110,10 +110,12 @@ int64_t segment_sum_workspace_bytes(int64_t E, int64_t nrows) {
   return 2 * align_up(E * 4) + 2 * align_up(nrows * 4) + align_up(static_cast<int64_t>(tmp));
 }
 
-// out (nrows, ncol) = per row, the sum of contrib[e] (ncol = 32 or 64 floats) over the entries e
-// with keys[e] == row, in ascending e; keys[e] >= nrows: skipped.
-int segment_sum(const uint32_t* keys, const float* contrib, int64_t E, int64_t nrows, int ncol, float* out, void* ws,
-                hipStream_t st) {
+// out (nrows, ncol) = per row, the sum of contrib[e * stride + offset ..] (ncol = 32 or 64 floats) over
+// the entries e with keys[e] == row, in ascending e; keys[e] >= nrows: skipped.  The contributions are
+// read in place: entry e's row may sit inside a wider record (the paper mode's d rows, 35 floats per
+// slot with the features at column 3; dvcp_group_rows_backward).
+int segment_sum_strided(const uint32_t* keys, const float* contrib, int64_t stride, int64_t offset, int64_t E,
+                        int64_t nrows, int ncol, float* out, void* ws, hipStream_t st) {
   if (ncol != 32 && ncol != 64) {
     set_error("segment_sum: %d columns (32 or 64)", ncol);
     return DVCP_EINVAL;
@@ -138,11 +140,17 @@ int segment_sum(const uint32_t* keys, const float* contrib, int64_t E, int64_t n
   hipLaunchKernelGGL(seg_bounds_kernel, dim3(ceil_div(E, 256)), dim3(256), 0, st, keys_out, E, nr, lo, hi);
   if (ncol == 32)
     hipLaunchKernelGGL(seg_sum_kernel<32>, dim3(ceil_div(nrows, 4)), dim3(256), 0, st, lo, hi, vals_out, contrib,
-                       nrows, out);
+                       stride, offset, nrows, out);
   else
     hipLaunchKernelGGL(seg_sum_kernel<64>, dim3(ceil_div(nrows, 4)), dim3(256), 0, st, lo, hi, vals_out, contrib,
-                       nrows, out);
+                       stride, offset, nrows, out);
   return launch_status("segment_sum");
+}
+
+// The packed form: entry e's contribution is the e-th row of a (E, ncol) array.
+int segment_sum(const uint32_t* keys, const float* contrib, int64_t E, int64_t nrows, int ncol, float* out, void* ws,
+                hipStream_t st) {
+  return segment_sum_strided(keys, contrib, ncol, 0, E, nrows, ncol, out, ws, st);
 }
 
 }  // namespace dvcp

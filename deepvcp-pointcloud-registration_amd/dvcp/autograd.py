@@ -26,7 +26,15 @@ Paper mode (dvcp/paper.py, not reference parity) adds the two links its stage he
 
   * ``cpg1d``      -- the second stage's 1-D CPG (dvcp_cpg1d / dvcp_cpg1d_backward);
   * ``weighting``  -- the paper's weighting layer (dvcp_weighting / dvcp_weighting_backward), whose
-                      scores are the pose solve's weights there and so do carry a gradient.
+                      scores are the pose solve's weights there and so do carry a gradient;
+
+and the links that train its extractor (``DeepVCPPaper(train_extractor=True)``):
+
+  * ``feature_propagation`` -- PointNetFeaturePropagation (dvcp_feature_propagation /
+                      dvcp_feature_propagation_backward: the 3-NN and the layer chain recomputed);
+  * ``group_rows`` -- the DFE rows' gather (dvcp_group_rows / dvcp_group_rows_backward);
+  * ``paper_feat_extraction`` -- PaperFeatExtraction: the three set abstractions (dvcp_sa_group_mlp /
+                      dvcp_sa_group_mlp_backward) and the three propagations, composed per layer.
 
 The key points, candidates and kNN indices carry no gradient in the reference either (index
 ops, knn_cuda under no_grad); the reference path's weighting layer gets none (only its top-k
@@ -332,6 +340,151 @@ def src_keypoints(fe_xyz, fe_feat, topk_idx, kstart, R_init, radius=1.0, nsample
 def pose_loss(x, y_pred, R_true, t_true, alpha):
     """deepVCP_loss.py:105-121 on (B, 3, n) operands -> (loss, R, t); differentiable in y_pred."""
     return _PoseLoss.apply(x, y_pred, R_true, t_true, alpha)
+
+
+# ---- paper mode: the extractor (dvcp.paper.PaperFeatExtraction) ------------------------------------
+
+def _layer_grads(gp, chans, weight_shapes):
+    """Packed per-layer dW | db | dgamma | dbeta -> [dW (as the conv's weight), db, dgamma, dbeta, ...]."""
+    out, o = [], 0
+    for (ci, co), shape in zip(zip(chans[:-1], chans[1:]), weight_shapes):
+        out += [gp[o:o + co * ci].view(shape), gp[o + co * ci:o + co * ci + co],
+                gp[o + co * ci + co:o + co * ci + 2 * co], gp[o + co * ci + 2 * co:o + co * ci + 3 * co]]
+        o += co * ci + 3 * co
+    return out
+
+
+def _wanted(ctx, first, grads, dtypes):
+    return [g.to(dt) if (g is not None and ctx.needs_input_grad[first + k]) else None
+            for k, (g, dt) in enumerate(zip(grads, dtypes))]
+
+
+class _FeatureProp(torch.autograd.Function):
+    """forward(fp, fc, xyz1, xyz2, p1, p2_rows, *[conv.weight, conv.bias, bn.weight, bn.bias per layer,
+    then fc.weight, fc.bias]): saves the operands only; the backward recomputes the rest."""
+
+    @staticmethod
+    def forward(ctx, fp, fc, xyz1, xyz2, p1, p2_rows, *params):
+        packed = fp.packed_params(fc)
+        parts = []
+        for bn in fp.mlp_bns:
+            parts += [bn.running_mean.float(), torch.rsqrt(bn.running_var.double() + bn.eps).float()]
+        if fc is not None:
+            n = fc.weight.shape[0]
+            parts += [torch.zeros(n, device=packed.device), torch.ones(n, device=packed.device)]
+        p2 = p2_rows.detach()
+        ctx.save_for_backward(xyz1, xyz2, p1, p2, packed, torch.cat(parts).contiguous())
+        ctx.chans = fp.chans + ([fc.weight.shape[0]] if fc is not None else [])
+        ctx.relu = [1] * len(fp.mlp_convs) + ([0] if fc is not None else [])
+        ctx.nconv = len(fp.mlp_convs)
+        ctx.shapes = [(p.shape, p.dtype) for p in params]
+        ctx.in_dtypes = (None if p1 is None else p1.dtype, p2_rows.dtype)
+        return ops.feature_propagation(xyz1, xyz2, p2, p1, ctx.chans, ctx.relu, packed)
+
+    @staticmethod
+    def backward(ctx, g):
+        xyz1, xyz2, p1, p2, packed, bnstat = ctx.saved_tensors
+        want_p1 = p1 is not None and ctx.needs_input_grad[4]
+        want_p2 = ctx.needs_input_grad[5]
+        gp, gp1, gp2 = ops.feature_propagation_backward(xyz1, xyz2, p2, p1, ctx.chans, ctx.relu, packed, bnstat, g,
+                                                        want_p1=want_p1, want_p2=want_p2)
+        wshapes = [ctx.shapes[4 * l][0] for l in range(ctx.nconv)] + [ctx.shapes[-2][0]]
+        per = _layer_grads(gp, ctx.chans, wshapes)
+        grads = per[:4 * ctx.nconv]
+        if len(ctx.chans) - 1 > ctx.nconv:      # the fused fc: its dgamma / dbeta are discarded
+            grads += per[4 * ctx.nconv:4 * ctx.nconv + 2]
+        gp1 = gp1.permute(0, 2, 1).to(ctx.in_dtypes[0]) if want_p1 else None
+        gp2 = gp2.to(ctx.in_dtypes[1]) if want_p2 else None
+        return (None, None, None, None, gp1, gp2, *_wanted(ctx, 6, grads, [dt for _, dt in ctx.shapes]))
+
+
+def _fp_tensors(fp, fc=None):
+    out = []
+    for conv, bn in zip(fp.mlp_convs, fp.mlp_bns):
+        out += [conv.weight, conv.bias, bn.weight, bn.bias]
+    return out + ([fc.weight, fc.bias] if fc is not None else [])
+
+
+def feature_propagation(fp, xyz1, xyz2, p1, p2_rows, fc=None):
+    """``fp.run`` (dvcp.paper.PointNetFeaturePropagation; dvcp_feature_propagation, the same kernel and
+    bits) -> (B, N1, C) rows, differentiable in p1 (B, D1, N1), p2_rows (B, N2, D2), the layers' conv and
+    BN weights and biases and the optional fused ``fc`` (backward: dvcp_feature_propagation_backward).
+    The eval-mode BN is folded as for the SA layers: the packed dgamma / dbeta are bn.weight's /
+    bn.bias' gradients, the running statistics are fixed."""
+    return _FeatureProp.apply(fp, fc, xyz1, xyz2, p1, p2_rows, *_fp_tensors(fp, fc))
+
+
+class _GroupRows(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, ctr, xyz, feat, count, lst, nsample, radius):
+        ctx.save_for_backward(count, lst)
+        ctx.cfg = (int(nsample), feat.shape[1], feat.dtype)
+        return ops.group_rows(ctr, xyz, feat.detach(), count, lst, nsample, radius)
+
+    @staticmethod
+    def backward(ctx, g):
+        count, lst = ctx.saved_tensors
+        ns, N, dtype = ctx.cfg
+        gfeat = ops.group_rows_backward(count, lst, ns, N, g).to(dtype) if ctx.needs_input_grad[2] else None
+        return None, None, gfeat, None, None, None, None
+
+
+def group_rows(ctr, xyz, feat, count, lst, nsample, radius):
+    """``ops.group_rows`` (ctr (B, Q, 3), xyz (B, 3, N), feat (B, N, 32)), differentiable in ``feat``
+    (dvcp_group_rows_backward; the coordinate columns carry no gradient)."""
+    return _GroupRows.apply(ctr, xyz, feat, count, lst, nsample, radius)
+
+
+class _SaGroupMlp(torch.autograd.Function):
+    """One set abstraction of the paper's extractor on fixed centres and lists: forward
+    dvcp_sa_group_mlp, backward dvcp_sa_group_mlp_backward (eval-mode BN)."""
+
+    @staticmethod
+    def forward(ctx, sa, xyz, ctr, feat, count, lst, ns, *params):
+        packed = sa.packed_params()
+        ctx.save_for_backward(xyz, ctr, feat, count, lst, packed, _bn_stats(sa))
+        ctx.chans, ctx.ns = list(sa.chans), int(ns)
+        ctx.shapes = [(p.shape, p.dtype) for p in params]
+        ctx.feat_dtype = None if feat is None else feat.dtype
+        return ops.sa_group_mlp(xyz, ctr, feat, count, lst, ns, sa.chans, packed, xyz_pdim=2, feat_ddim=1, feat_pdim=2)
+
+    @staticmethod
+    def backward(ctx, g):
+        xyz, ctr, feat, count, lst, packed, bnstat = ctx.saved_tensors
+        want_feat = feat is not None and ctx.needs_input_grad[3]
+        gp, gF = ops.sa_group_mlp_backward(xyz, ctr, feat, count, lst, ctx.ns, ctx.chans, packed, bnstat, g,
+                                           want_feat_grad=want_feat)
+        grads = _layer_grads(gp, ctx.chans, [ctx.shapes[4 * l][0] for l in range(len(ctx.chans) - 1)])
+        gF = gF.permute(0, 2, 1).to(ctx.feat_dtype) if want_feat else None
+        return (None, None, None, gF, None, None, None, *_wanted(ctx, 7, grads, [dt for _, dt in ctx.shapes]))
+
+
+def paper_feat_extraction(fe, pts, starts):
+    """``PaperFeatExtraction.forward`` (pts (B, C, N), starts (3, B)) -> (B, N, 32), the same kernels and
+    bits, differentiable in every parameter of ``fe``.  FPS and the ball queries run as in inference
+    and carry no gradient; each set abstraction is paired with dvcp_sa_group_mlp_backward and each
+    propagation with dvcp_feature_propagation_backward; torch adds a level's two consumers (f1: fp2's
+    d p1 + sa2's feature gradient; f2: fp3's + sa3's).  Saved for backward: per level the coordinates,
+    centres, counts, lists and feature rows.  The SA backward's feature scatter uses float atomics, so
+    gradients upstream of it (sa1, sa2) are not bit-reproducible."""
+    B, _, N = pts.shape
+    xyz = pts[:, :3, :]
+    feat = pts[:, 3:, :] if fe.use_normal else None
+    levels = [(xyz, feat)]
+    for sa, st in zip((fe.sa1, fe.sa2, fe.sa3), starts):
+        pxyz, pf = levels[-1]
+        with torch.no_grad():
+            _, c = ops.fps(pxyz, sa.npoint, st.to(pts.device), pdim=2)
+            ns = min(int(sa.nsample), pxyz.shape[2])
+            count, lst, _ = ops.ball_query(pxyz, c, sa.radius, ns, pdim=2, cdim_pts=2)
+        rows = _SaGroupMlp.apply(sa, pxyz, c, pf, count, lst, ns,
+                                 *[t for conv, bn in zip(sa.mlp_convs, sa.mlp_bns)
+                                   for t in (conv.weight, conv.bias, bn.weight, bn.bias)])
+        levels.append((c, rows.permute(0, 2, 1)))
+    (x0, f0), (x1, f1), (x2, f2), (x3, f3) = levels
+    g2 = feature_propagation(fe.fp3, x2, x3, f2, f3.permute(0, 2, 1))
+    g1 = feature_propagation(fe.fp2, x1, x2, f1, g2)
+    return feature_propagation(fe.fp1, x0, x1, f0, g1, fc=fe.fc)
 
 
 def _linears(m):

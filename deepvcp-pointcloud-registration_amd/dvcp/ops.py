@@ -1206,6 +1206,80 @@ def weighting_backward(feat, params, grad_score, want_feat=True):
     return gp, gfeat
 
 
+def fp_nparams(chans):
+    """Packed size of a propagation's parameters and of their gradient: (ci co + 3 co) per layer."""
+    return sum(a * b + 3 * b for a, b in zip(chans[:-1], chans[1:]))
+
+
+def feature_propagation_backward(xyz1, xyz2, p2_rows, p1, chans, relu, params, bnstat, grad_out, want_p1=True,
+                                 want_p2=True):
+    """Gradients of ``feature_propagation`` (same operands; ``bnstat``: per layer running_mean |
+    rsqrt(running_var + eps), 0 | 1 for a fused fc): (d params, per layer dW | db | dgamma | dbeta,
+    summed in a fixed order; d p1 (B, N1, D1) or None; d p2_rows (B, N2, D2) or None).  The 3-NN, the
+    weights and the layer chain are recomputed (nothing is saved by the forward); identical calls give
+    identical bits."""
+    _lib.require_gpu(xyz1, xyz2, p2_rows, params, bnstat, grad_out)
+    B = xyz1.shape[0]
+    N1, x1b, x1c, x1n = _pts(xyz1, 2)
+    N2, x2b, x2c, x2n = _pts(xyz2, 2)
+    if p2_rows.dtype != torch.float32 or p2_rows.stride(2) != 1:
+        raise ValueError("feature_propagation_backward: p2 rows must be fp32 with contiguous channels")
+    D2 = p2_rows.shape[2]
+    if p1 is not None:
+        if p1.dtype != torch.float32:
+            p1 = p1.float()
+        D1, (p1b, p1d, p1n) = p1.shape[1], p1.stride()
+    else:
+        D1, p1b, p1d, p1n = 0, 0, 0, 0
+    chans = list(chans)
+    if grad_out.numel() != B * N1 * chans[-1]:
+        raise RuntimeError(f"feature_propagation_backward: grad_out {tuple(grad_out.shape)} is not "
+                           f"({B}, {N1}, {chans[-1]})")
+    dev = xyz1.device
+    ch = torch.tensor(chans, dtype=torch.int32)
+    rl = torch.tensor([int(bool(r)) for r in relu], dtype=torch.int32)
+    g = grad_out.reshape(B, N1, chans[-1]).float().contiguous()
+    want_p1 = bool(want_p1) and D1 > 0
+    gp = torch.empty(fp_nparams(chans), dtype=torch.float32, device=dev)
+    gp1 = torch.empty(B, N1, D1, dtype=torch.float32, device=dev) if want_p1 else None
+    gp2 = torch.empty(B, N2, D2, dtype=torch.float32, device=dev) if want_p2 else None
+    nbytes = int(_lib.load().dvcp_feature_propagation_backward_workspace_bytes(B, N1, N2, D2, len(chans) - 1,
+                                                                               ch.data_ptr(), int(bool(want_p2))))
+    if nbytes < 0:
+        raise RuntimeError("dvcp_feature_propagation_backward_workspace_bytes: size query failed")
+    ws = _workspace(nbytes, dev)
+    macs = sum(a * b for a, b in zip(chans[:-1], chans[1:]))
+    call("dvcp_feature_propagation_backward", ptr(xyz1), x1b, x1c, x1n, N1, ptr(xyz2), x2b, x2c, x2n, N2, B, ptr(p1),
+         p1b, p1d, p1n, D1, ptr(p2_rows), p2_rows.stride(0), p2_rows.stride(1), D2, len(chans) - 1, ptr(ch), ptr(rl),
+         ptr(params), ptr(bnstat), ptr(g), ptr(gp1), ptr(gp2), ptr(ws), ws.numel() * 4, ptr(gp), stream(),
+         work=(B * N1 * (9.0 * N2 + 2.0 * macs * (3 if (want_p1 or want_p2) else 2)),
+               4.0 * B * (3 * (N1 + N2) + N2 * D2 + N1 * (D1 + chans[-1]) + (N1 * D1 if want_p1 else 0)
+                          + (N1 * 3 * D2 * 2 + N2 * D2 if want_p2 else 0))))
+    return gp, gp1, gp2
+
+
+def group_rows_backward(count, lst, nsample, N, grad_rows):
+    """Gradient of ``group_rows`` in the features: d rows (B, Q, nsample, 35) -> d feat (B, N, 32), each
+    point's slots added in entry order (identical calls give identical bits); padded slots add to the
+    first hit, empty neighbourhoods route nothing, points in no list get 0."""
+    _lib.require_gpu(count, lst, grad_rows)
+    B, Q, ns_list = lst.shape
+    if grad_rows.dim() != 4 or tuple(grad_rows.shape[:3]) != (B, Q, int(nsample)):
+        raise RuntimeError(f"group_rows_backward: grad_rows {tuple(grad_rows.shape)} does not match lists "
+                           f"{tuple(lst.shape)} and nsample {nsample}")
+    D = grad_rows.shape[3] - 3
+    g = grad_rows.float().contiguous()
+    gfeat = torch.empty(B, int(N), D, dtype=torch.float32, device=g.device)
+    nbytes = int(_lib.load().dvcp_group_rows_backward_workspace_bytes(B, Q, int(N), int(nsample)))
+    if nbytes < 0:
+        raise RuntimeError("dvcp_group_rows_backward_workspace_bytes: size query failed")
+    ws = _workspace(nbytes, g.device)
+    call("dvcp_group_rows_backward", ptr(count), ptr(lst), ns_list, int(nsample), Q, int(N), D, B, ptr(g), ptr(gfeat),
+         ptr(ws), ws.numel() * 4, stream(),
+         work=(1.0 * B * Q * nsample * D, 4.0 * B * (Q * nsample * (D + 3) + N * D)))
+    return gfeat
+
+
 def paper_pose(x, y, w, reflection_fix=True, inlier_ratio=1.0, R_true=None, t_true=None):
     """Weighted Kabsch with reflection fix and the paper's outlier rejection on (B, 3, n) fp64
     operands (w (B, n) or None) -> R (B, 3, 3), t (B, 3, 1)[, partial (B, 2) with R_true, t_true]."""

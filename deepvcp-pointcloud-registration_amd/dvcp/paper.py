@@ -17,7 +17,9 @@ choices the paper leaves open.
   * ``DeepVCPPaper`` -- the whole network with duplication (Sec. 3.6): a shared feature extractor
     and two cascaded stages, the second fed with the first's pose and generating candidates on a
     z line scored by a 1-D CNN (dvcp_cpg1d).  Inference by default; ``train_heads=True`` trains
-    the two stages' heads (weighting layer, DFE, CPG) with the extractor frozen.
+    the two stages' heads (weighting layer, DFE, CPG) with the extractor frozen, and
+    ``train_extractor=True`` the extractor with them (dvcp_feature_propagation_backward,
+    dvcp_group_rows_backward, dvcp_sa_group_mlp_backward).
 """
 import torch
 import torch.nn as nn
@@ -83,7 +85,10 @@ def deepVCP_loss_paper(src_keypts, tgt_vcp, weights, R_true, t_true, alpha=0.5, 
 class PointNetFeaturePropagation(nn.Module):
     """pointnet2_utils.py:265-315 (same parameters and state_dict keys: mlp_convs.i, mlp_bns.i);
     forward(xyz1 (B, 3, N), xyz2 (B, 3, S), points1 (B, D1, N) or None, points2 (B, D2, S)) ->
-    (B, D', N), one HIP launch (eval-mode BN folded; inference only)."""
+    (B, D', N), one HIP launch (eval-mode BN folded).  In eval mode with autograd on and a parameter or
+    a feature input requiring a gradient, the output carries one (``autograd.feature_propagation``:
+    the same forward kernel and bits, backward dvcp_feature_propagation_backward); training mode
+    (batch-statistics BN) is refused."""
 
     def __init__(self, in_channel, mlp):
         super().__init__()
@@ -124,7 +129,10 @@ class PointNetFeaturePropagation(nn.Module):
 
     def forward(self, xyz1, xyz2, points1, points2):
         _inference_only(self)
-        rows = self.run(xyz1, xyz2, points1, points2.permute(0, 2, 1).contiguous().float())
+        p2_rows = points2.permute(0, 2, 1).contiguous().float()
+        if _wants_grad(self, points2, *(() if points1 is None else (points1,))):
+            return autograd.feature_propagation(self, xyz1, xyz2, points1, p2_rows).permute(0, 2, 1)
+        rows = self.run(xyz1, xyz2, points1, p2_rows)
         return rows.permute(0, 2, 1)
 
 
@@ -141,7 +149,9 @@ def paper_fe_config(use_normal=False, npoints=(4096, 1024, 256), radii=(0.1, 0.2
 
 class PaperFeatExtraction(nn.Module):
     """Paper Sec. 3.1: per-point features (B, N, 32) for every input point.  forward(pts (B, C, N),
-    starts=None (3, B) FPS starts, drawn like the reference's sample_and_group when None)."""
+    starts=None (3, B) FPS starts, drawn like the reference's sample_and_group when None).  In eval mode
+    with autograd on and a parameter (or ``pts``) requiring a gradient the features carry one
+    (``autograd.paper_feat_extraction``: the same kernels and bits); ``.train()`` is refused."""
 
     def __init__(self, use_normal=False, **cfg):
         super().__init__()
@@ -160,6 +170,8 @@ class PaperFeatExtraction(nn.Module):
         B, _, N = pts.shape
         if starts is None:
             starts = self.draw_starts(B, N)
+        if _wants_grad(self, pts):
+            return autograd.paper_feat_extraction(self, pts, starts)
         xyz = pts[:, :3, :]
         feat = pts[:, 3:, :] if self.use_normal else None
         levels = [(xyz, feat)]
@@ -274,12 +286,23 @@ class DeepVCPPaper(nn.Module):
     in eval mode (``.train()`` is refused as before).
     Memory: the materialised target rows (B, K C, 32, 35) fp32 are saved for backward: 4 * 32 * 35 *
     K * C bytes per pair, about 381 MB at K = 64, C = 1331 (computed, not measured); fusing them as the
-    reference path's dvcp_dfe_tgt does is a later step."""
+    reference path's dvcp_dfe_tgt does is a later step.
+
+    ``train_extractor`` (a plain attribute too).  True, in eval mode with autograd on: head training as
+    above, and the extractor's trainable parameters train with it.  FE runs recorded for both clouds
+    (``autograd.paper_feat_extraction``; the same parameters, so their gradients add); the full-cloud
+    scores and the top-k stay under no_grad on the detached features; the K rows' scores are recomputed
+    on the gathered, recorded features (dvcp_weighting_backward then returns d feat); the source and
+    target rows go through ``autograd.group_rows`` and ``autograd.dfe_rows`` returns d rows (another
+    4 * 32 * 35 * K * C bytes per pair on the target side while backward runs).  A frozen extractor
+    under ``train_extractor=True`` is head training, bit for bit.  With the switch off nothing changes,
+    the refusal under ``train_heads=True`` included."""
 
     def __init__(self, use_normal=False, K=64, r=2.0, s=0.4, s_z=0.25, d=1.0, nsample=32, duplication=True,
-                 inlier_ratio=0.8, train_heads=False, **fe_cfg):
+                 inlier_ratio=0.8, train_heads=False, train_extractor=False, **fe_cfg):
         super().__init__()
         self.train_heads = bool(train_heads)
+        self.train_extractor = bool(train_extractor)
         self.FE = PaperFeatExtraction(use_normal, **fe_cfg)
         self.stages = nn.ModuleList([_Stage(False)] + ([_Stage(True)] if duplication else []))
         self.K, self.r, self.s, self.s_z, self.d, self.ns = K, r, s, s_z, d, nsample
@@ -287,9 +310,9 @@ class DeepVCPPaper(nn.Module):
 
     def forward(self, src, tgt, R_init, t_init, starts=None, keypoint_idx=None):
         _inference_only(self)
-        train = self.train_heads and torch.is_grad_enabled()
+        train = (self.train_heads or self.train_extractor) and torch.is_grad_enabled()
         if train:
-            if any(p.requires_grad for p in self.FE.parameters()):
+            if not self.train_extractor and any(p.requires_grad for p in self.FE.parameters()):
                 raise NotImplementedError("dvcp: DeepVCPPaper(train_heads=True) trains the stage heads only: the "
                                           "extractor must be frozen (model.FE.requires_grad_(False))")
             autograd.require_trainable_grid(int(2 * self.r / self.s + 1), self.stages[0].cpg.train_large_grid)
@@ -302,8 +325,9 @@ class DeepVCPPaper(nn.Module):
         dev = src.device
         if starts is None:
             starts = torch.stack([self.FE.draw_starts(B, N), self.FE.draw_starts(B, tgt.shape[2])])
-        with torch.no_grad():
-            f_src, f_tgt = self.FE(src, starts[0]), self.FE(tgt, starts[1])
+        with torch.enable_grad() if (train and self.train_extractor) else torch.no_grad():
+            f_src, f_tgt = self.FE(src, starts[0]), self.FE(tgt, starts[1])   # recorded: trainable FE parameters
+        rows_of = lambda f: autograd.group_rows if f.requires_grad else ops.group_rows   # noqa: E731
         xs, xt = src[:, :3, :], tgt[:, :3, :]
         xs_rows = xs.permute(0, 2, 1)
         Rc = R_init.to(dev, torch.float64).expand(B, 3, 3)
@@ -311,7 +335,7 @@ class DeepVCPPaper(nn.Module):
         out = []
         for si, st in enumerate(self.stages):
             with torch.no_grad():
-                score = st.WL(f_src)
+                score = st.WL(f_src.detach())
             top = ops.topk(score, self.K) if keypoint_idx is None else keypoint_idx[si].to(dev, torch.int64)
             if train:   # the K selected rows again, recorded: the gathered scores bit for bit
                 w = st.WL(torch.gather(f_src, 1, top[..., None].expand(B, self.K, 32)))
@@ -320,7 +344,7 @@ class DeepVCPPaper(nn.Module):
             kp = torch.gather(xs_rows, 1, top[..., None].expand(B, self.K, 3)).contiguous()   # (B, K, 3)
             ns_src = min(self.ns, N)
             cnt, lst, _ = ops.ball_query(xs, kp, self.d, ns_src, pdim=2, cdim_pts=1)
-            rows = ops.group_rows(kp, xs, f_src, cnt, lst, self.ns, self.d)
+            rows = rows_of(f_src)(kp, xs, f_src, cnt, lst, self.ns, self.d)
             dfe = (lambda X: autograd.dfe_rows(X, st.DFE)) if train else (lambda X: ops.dfe(X, st.DFE.packed_params()))
             src_dfe = dfe(rows)                                                              # (B, K, 32)
             moved = torch.einsum("bij,bkj->bki", Rc, kp.double()) + tc[:, None, :]
@@ -336,7 +360,7 @@ class DeepVCPPaper(nn.Module):
             qry = cand.view(B, self.K * C, 3)
             ns_tgt = min(self.ns, xt.shape[2])
             cnt, lst, _ = ops.ball_query(xt, qry, self.d, ns_tgt, pdim=2, cdim_pts=1)
-            trows = ops.group_rows(qry, xt, f_tgt, cnt, lst, self.ns, self.d)
+            trows = rows_of(f_tgt)(qry, xt, f_tgt, cnt, lst, self.ns, self.d)
             tgt_dfe = dfe(trows).view(B, self.K, C, 32)    # train: trows (B, K C, 32, 35) saved for backward
             # 3-D: cpg.py:34's reshape of a (B, K, 32, C) view whose row-major order is the
             # candidates' own: the 3-D grid without the reference's Q11 scramble

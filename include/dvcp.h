@@ -547,6 +547,40 @@ int64_t dvcp_weighting_backward_workspace_bytes(int P);
 int dvcp_weighting_backward(const float* feat, int P, const float* params, const float* grad_score,
                             float* grad_feat, void* workspace, int64_t ws_bytes, float* grad_params,
                             void* stream);
+/* Backward of dvcp_feature_propagation (training of the paper's extractor).  Nothing is saved by the
+ * forward: the 3-NN, the interpolation weights and the layer chain are recomputed per tile of 32
+ * rows with the forward's own arithmetic, so the neighbours and the ReLU masks are the forward's.
+ * Arguments up to params: as dvcp_feature_propagation (same limits: nlayer <= 4, chans[0] <= 128,
+ * every layer output <= 64, N2 = 2 refused).  bnstat: per layer running_mean | 1 / sqrt(running_var
+ * + eps) (chans[l + 1] floats each; 0 | 1 for a plain fully connected layer, whose dgamma / dbeta
+ * the caller discards); grad_out: B x N1 x chans[nlayer] fp32.
+ * grad_params: per layer dW | db | dgamma | dbeta (the layout of dvcp_sa_group_mlp_backward), summed
+ * in a fixed order (per-workgroup partial rows in workspace, folded in index order in fp64).
+ * grad_p1 (optional): B x N1 x D1, one writer per element.  grad_p2 (optional): B x N2 x D2, the three
+ * neighbours' rows added per target point in entry order (segment sums, no float atomics); wanted
+ * only with D2 = 32 or 64.  Coordinates carry no gradient.  Two identical calls give identical bits.
+ * workspace: ws_bytes >= dvcp_feature_propagation_backward_workspace_bytes(B, N1, N2, D2, nlayer,
+ * chans, grad_p2 != NULL) bytes.  B = 0 or N1 = 0: grad_params (and grad_p2) are zeroed. */
+int64_t dvcp_feature_propagation_backward_workspace_bytes(int B, int N1, int N2, int D2, int nlayer,
+                                                          const int* chans, int want_p2);
+int dvcp_feature_propagation_backward(const float* xyz1, int64_t x1b, int64_t x1c, int64_t x1n, int N1,
+                                      const float* xyz2, int64_t x2b, int64_t x2c, int64_t x2n, int N2, int B,
+                                      const float* p1, int64_t p1b, int64_t p1d, int64_t p1n, int D1,
+                                      const float* p2, int64_t p2b, int64_t p2n, int D2, int nlayer,
+                                      const int* chans, const int* relu, const float* params,
+                                      const float* bnstat, const float* grad_out, float* grad_p1,
+                                      float* grad_p2, void* workspace, int64_t ws_bytes, float* grad_params,
+                                      void* stream);
+/* Backward of dvcp_group_rows in the features: grad_rows B x Q x ns_out x (3 + D) -> grad_feat
+ * B x N x D (D = 32 only).  Slot `slot` of centre (b, q) adds its feature columns to point
+ * list[(b Q + q) ns_list + (slot < count ? slot : 0)] (padded slots: the first hit); count <= 0 routes
+ * nothing; points in no list get 0.  The three coordinate columns carry no gradient.  The rows are
+ * read in place and added per point in entry order (segment sums): identical bits on identical
+ * calls.  workspace: ws_bytes >= dvcp_group_rows_backward_workspace_bytes(B, Q, N, ns_out) bytes. */
+int64_t dvcp_group_rows_backward_workspace_bytes(int B, int Q, int N, int ns_out);
+int dvcp_group_rows_backward(const int32_t* count, const int32_t* list, int ns_list, int ns_out, int Q, int N,
+                             int D, int B, const float* grad_rows, float* grad_feat, void* workspace,
+                             int64_t ws_bytes, void* stream);
 
 /* Corresponding point generation.  Replaces cpg.py:27-60: cost volume
  * (src - scrambled tgt)^2 (Q11), Conv3d 32-16-4-1 (k3, p1, no activations), softmax over C,
