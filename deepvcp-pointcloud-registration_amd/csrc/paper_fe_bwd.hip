@@ -20,6 +20,9 @@
 //                         neighbours: entry e = (b N1 + n) 3 + i gets the key b N2 + idx_i (the
 //                         sentinel for i >= min(N2, 3)) and the row w_i g_x[D1..], and segment_sum
 //                         (segsum.hip) adds the rows per target point in entry order.
+//                         The kernel is a template over four modes (kFbEval: the above, today's bits;
+//                         kFbStats / kFbSums / kFbGrad: the batch-statistics passes of training mode,
+//                         see the constants below).
 //   group_rows_keys_kernel  backward of group_rows_kernel: slot `slot` of centre (b, q) routes its 32
 //                         feature columns to point list[bq ns_list + (slot < cnt ? slot : 0)] (padded
 //                         slots add to the first hit's row; cnt <= 0 routes nothing).  The kernel only
@@ -103,12 +106,42 @@ __device__ __forceinline__ void fb_store(const float (&dW)[NK], float db, float 
   }
 }
 
+// fp_bwd_kernel's modes.  kFbEval: eval-mode BN (running statistics), the gradient pass.  The other
+// three are the batch-statistics passes (training mode; torch's batch-norm backward,
+// dz_l = scale_l (g_a - A_l/M - xhat_l B_l/M), xhat = (z - mean) rstd, A_l = sum g_a, B_l = sum g_a xhat):
+// kFbStats: sum z | sum z^2 of layer kl's conv output over the B N1 rows (the forward chain up to kl);
+// kFbSums: A | B of layer kl, given those of the layers above; kFbGrad: the gradient pass, given all.
+// Every such sum is taken in fp64 from the single entries: thread (o, kq) owns channel o over the rows
+// kq, kq + 4, ... of every tile its workgroup walks; one partial row per (workgroup, kq), folded in
+// index order by fb_fold_sums_kernel.  xhat and the mean terms are evaluated in fp64 from fp64
+// statistics (bn64: per layer mean | rstd | A/M | B/M; 0 | 1 | 0 | 0 for a fused fc, a plain layer).
+constexpr int kFbEval = -1, kFbGrad = 0, kFbSums = 1, kFbStats = 2;
+constexpr int kFbSumRow = 2 * kFpMaxCo;  // doubles per partial row of sums
+
+// the walked layer's mean | rstd | A/M | B/M (batch-statistics modes only: no LDS in the eval kernel)
+__device__ __forceinline__ double* fb_bn_vectors() {
+  __shared__ double v[4 * kFpMaxCo];
+  return v;
+}
+
+// out[e], e < 2 co: sum over the n partial rows, k ascending (first co entries, then those at kFpMaxCo)
+__global__ __launch_bounds__(128) void fb_fold_sums_kernel(const double* __restrict__ part, int n, int co,
+                                                           double* __restrict__ out) {
+  const int e = threadIdx.x;
+  if (e >= 2 * co) return;
+  const int src = e < co ? e : kFpMaxCo + (e - co);
+  double acc = 0.0;
+  for (int k = 0; k < n; ++k) acc += part[static_cast<int64_t>(k) * kFbSumRow + src];
+  out[e] = acc;
+}
+
+template <int MODE>
 __global__ __launch_bounds__(kFpThreads) void fp_bwd_kernel(
     PointsView<float> xyz1, int N1, PointsView<float> xyz2, int N2, int B, const float* __restrict__ p1, int64_t p1b,
     int64_t p1d, int64_t p1n, int D1, const float* __restrict__ p2, int64_t p2b, int64_t p2n, int D2, FpLayers lay,
     const float* __restrict__ params, const float* __restrict__ bnstat, const float* __restrict__ gout,
     float* __restrict__ gp1, uint32_t* __restrict__ keys, float* __restrict__ contrib, int nparams,
-    float* __restrict__ partial) {
+    float* __restrict__ partial, const double* __restrict__ bn64, int kl, double* __restrict__ sum_partial) {
   __shared__ float4 tile[kFpTile + 8];                      // 3-NN scan; afterwards the gradient rows gA
   __shared__ float x0[kFpRows * kFbLdX];                    // layer-0 input rows
   __shared__ float hb[kFpMaxL - 1][kFpRows * kFbLdH];       // inputs of layers 1..L-1
@@ -136,6 +169,8 @@ __global__ __launch_bounds__(kFpThreads) void fp_bwd_kernel(
   for (int j = 0; j < kFbNk; ++j) dW1[j] = dW2[j] = dW3[j] = 0.f;
 #pragma unroll
   for (int l = 0; l < kFpMaxL; ++l) db[l] = dg[l] = dbe[l] = 0.f;
+  double sumA = 0.0, sumB = 0.0;             // kFbStats: sum z, sum z^2; kFbSums: A, B (channel o, rows kq + 4 j)
+  const int Lf = MODE == kFbStats ? kl : L;  // layers of the forward chain this pass needs
 
   for (int t = blockIdx.x; t < tiles; t += gridDim.x) {
     const int b = t / tpb, r0 = (t % tpb) * kFpRows;
@@ -213,7 +248,7 @@ __global__ __launch_bounds__(kFpThreads) void fp_bwd_kernel(
     }
     // ---- the layer chain, the forward's arithmetic; the last layer turns grad_out into its g_a
     const float* P = params;
-    for (int l = 0; l < L; ++l) {
+    for (int l = 0; l < Lf; ++l) {
       const int ci = lay.ch[l], co = lay.ch[l + 1];
       const float* in = l == 0 ? x0 : hb[l - 1];
       const int ldi = l == 0 ? kFbLdX : kFbLdH;
@@ -235,7 +270,7 @@ __global__ __launch_bounds__(kFpThreads) void fp_bwd_kernel(
         if (l < L - 1) {
           if (lay.relu[l]) v = v > 0.f ? v : 0.f;
           hb[l][rr * kFbLdH + oc] = v;
-        } else {
+        } else if constexpr (MODE != kFbStats) {
           const int nn = r0 + rr;
           float g = nn < N1 ? gout[(static_cast<int64_t>(b) * N1 + nn) * co + oc] : 0.f;
           if (lay.relu[l] && !(v > 0.f)) g = 0.f;
@@ -243,6 +278,17 @@ __global__ __launch_bounds__(kFpThreads) void fp_bwd_kernel(
         }
       }
       if (l < L - 1) P += ci * co + 3 * co;
+    }
+    if constexpr (MODE == kFbStats) {  // layer kl's z over the tile's real rows; nothing is walked back
+      __syncthreads();
+      if (o < lay.ch[kl]) {
+        for (int rr = kq; rr < kFpRows && r0 + rr < N1; rr += 4) {
+          const double zd = static_cast<double>(zb[kl - 1][rr * kFbLdH + o]);
+          sumA += zd;
+          sumB += zd * zd;
+        }
+      }
+      continue;
     }
     // ---- the walk back; P points at layer l's parameters, wsh / bsh hold layer L - 1's
     const bool want_x = gp1 || contrib;
@@ -256,13 +302,43 @@ __global__ __launch_bounds__(kFpThreads) void fp_bwd_kernel(
         for (int e = tid; e < co; e += kFpThreads) bsh[1][e] = P[ci * co + co + e];
         __syncthreads();
       }
-      for (int e = tid; e < kFpRows * co; e += kFpThreads) {
-        const int rr = e / co, oc = e % co;
-        gZ[rr * kFbLdH + oc] = gA[rr * kFbLdX + oc] * bsh[1][oc];
+      if constexpr (MODE == kFbEval) {
+        for (int e = tid; e < kFpRows * co; e += kFpThreads) {
+          const int rr = e / co, oc = e % co;
+          gZ[rr * kFbLdH + oc] = gA[rr * kFbLdX + oc] * bsh[1][oc];
+        }
+      } else {
+        double* bnv = fb_bn_vectors();
+        for (int e = tid; e < 4 * co; e += kFpThreads) bnv[(e / co) * kFpMaxCo + e % co] = bn64[2 * soff + e];
+        __syncthreads();
+        if (MODE == kFbSums && l == kl - 1) {  // this layer's A | B, then on to the next tile
+          if (o < co) {
+            for (int rr = kq; rr < kFpRows; rr += 4) {
+              const double ga = static_cast<double>(gA[rr * kFbLdX + o]);
+              const double xh = (static_cast<double>(zb[l][rr * kFbLdH + o]) - bnv[o]) * bnv[kFpMaxCo + o];
+              sumA += ga;
+              sumB += ga * xh;
+            }
+          }
+          break;
+        }
+        for (int e = tid; e < kFpRows * co; e += kFpThreads) {
+          const int rr = e / co, oc = e % co;
+          float gz = 0.f;  // rows past N1 are no entries of the batch
+          if (r0 + rr < N1) {
+            const double xh = (static_cast<double>(zb[l][rr * kFbLdH + oc]) - bnv[oc]) * bnv[kFpMaxCo + oc];
+            gz = static_cast<float>(static_cast<double>(bsh[1][oc]) *
+                                    ((static_cast<double>(gA[rr * kFbLdX + oc]) - bnv[2 * kFpMaxCo + oc]) -
+                                     xh * bnv[3 * kFpMaxCo + oc]));
+          }
+          gZ[rr * kFbLdH + oc] = gz;
+        }
       }
       __syncthreads();
-      if (o < co) {
-        const float mean = bnstat[soff + o], rstd = bnstat[soff + co + o];
+      if (MODE != kFbSums && o < co) {
+        // (kFbGrad: the fp32 dgamma / dbeta are by-products; the caller takes B and A of the sums passes)
+        const float mean = MODE == kFbEval ? bnstat[soff + o] : static_cast<float>(bn64[2 * soff + o]);
+        const float rstd = MODE == kFbEval ? bnstat[soff + co + o] : static_cast<float>(bn64[2 * soff + co + o]);
         switch (l) {
           case 0:
             fb_accumulate<kFbNk0>(dW0, db[0], dg[0], dbe[0], gA, gZ, zb[0], x0, kFbLdX, ci, mean, rstd, o, kq);
@@ -294,6 +370,7 @@ __global__ __launch_bounds__(kFpThreads) void fp_bwd_kernel(
       }
     }
     __syncthreads();
+    if constexpr (MODE == kFbSums) continue;
     // ---- d points1 (one writer per element) and the three neighbours' entries of d points2
     if (gp1) {
       for (int e = tid; e < kFpRows * D1; e += kFpThreads) {
@@ -316,6 +393,12 @@ __global__ __launch_bounds__(kFpThreads) void fp_bwd_kernel(
           contrib[((static_cast<int64_t>(b) * N1 + nn) * 3 + i) * D2 + cc] = nwt[rr][i] * gA[rr * kFbLdX + D1 + cc];
       }
     }
+  }
+  if constexpr (MODE == kFbStats || MODE == kFbSums) {
+    double* so = sum_partial + (static_cast<int64_t>(blockIdx.x) * 4 + kq) * kFbSumRow;
+    so[o] = sumA;
+    so[kFpMaxCo + o] = sumB;
+    return;
   }
   // ---- this workgroup's partial row: per layer dW | db | dgamma | dbeta
   float* po = partial + static_cast<int64_t>(blockIdx.x) * nparams;
@@ -423,14 +506,155 @@ extern "C" int dvcp_feature_propagation_backward(
     contrib = reinterpret_cast<float*>(w);
     w += dvcp::fb_align(E * D2 * 4);
   }
-  hipLaunchKernelGGL(dvcp::fp_bwd_kernel, dim3(grid), dim3(dvcp::kFpThreads), 0, st,
+  hipLaunchKernelGGL(dvcp::fp_bwd_kernel<dvcp::kFbEval>, dim3(grid), dim3(dvcp::kFpThreads), 0, st,
                      dvcp::PointsView<float>{xyz1, x1b, x1c, x1n}, N1, dvcp::PointsView<float>{xyz2, x2b, x2c, x2n}, N2,
                      B, p1, p1b, p1d, p1n, D1, p2, p2b, p2n, D2, lay, params, bnstat, grad_out, grad_p1, keys, contrib,
-                     np, partial);
+                     np, partial, nullptr, 0, nullptr);
   if (int e = dvcp::launch_status("dvcp_feature_propagation_backward")) return e;
   hipLaunchKernelGGL(dvcp::fe_fold_partials_kernel, dim3(dvcp::ceil_div(np, 256)), dim3(256), 0, st, partial, grid, np,
                      grad_params);
   if (int e = dvcp::launch_status("dvcp_feature_propagation_backward(sum)")) return e;
+  if (grad_p2) return dvcp::segment_sum(keys, contrib, E, static_cast<int64_t>(B) * N2, D2, grad_p2, w, st);
+  return DVCP_OK;
+}
+
+// ------------------------------------------------- feature propagation under batch statistics
+static int fb_bn_layers(const char* who, int N1, int N2, int B, int D1, int D2, int nlayer, const int* chans,
+                        const int* relu, dvcp::FpLayers* lay) {
+  DVCP_REQUIRE(chans && relu, "%s: null pointer", who);
+  DVCP_REQUIRE(N1 >= 0 && N2 >= 1 && B >= 0 && B <= 65535 && D1 >= 0 && D2 >= 1,
+               "%s: bad sizes N1=%d N2=%d B=%d D1=%d D2=%d", who, N1, N2, B, D1, D2);
+  DVCP_REQUIRE(N2 != 2, "%s: N2 = 2 (refused like the forward: the reference's weight.view(B, N, 3, 1), "
+               "pointnet2_utils.py:303, fails for two interpolation points)", who);
+  DVCP_REQUIRE(nlayer >= 1 && nlayer <= dvcp::kFpMaxL, "%s: 1..%d layers", who, dvcp::kFpMaxL);
+  DVCP_REQUIRE(chans[0] == D1 + D2, "%s: chans[0]=%d != D1 + D2", who, chans[0]);
+  lay->L = nlayer;
+  for (int l = 0; l <= nlayer; ++l) {
+    DVCP_REQUIRE(chans[l] >= 1 && chans[l] <= (l == 0 ? dvcp::kFpMaxC : dvcp::kFpMaxCo),
+                 "%s: layer width %d out of range", who, chans[l]);
+    lay->ch[l] = chans[l];
+  }
+  for (int l = 0; l < nlayer; ++l) lay->relu[l] = relu[l] != 0;
+  DVCP_REQUIRE(static_cast<int64_t>(B) * N1 * 3 <= 0x7FFFFFFF && static_cast<int64_t>(B) * N2 <= 0x7FFFFFFF,
+               "%s: B N1 3 and B N2 must stay below 2^31", who);
+  return DVCP_OK;
+}
+
+static int64_t fb_sum_bytes(int64_t tiles) {
+  return dvcp::fb_align(static_cast<int64_t>(dvcp::fb_grid(tiles)) * 4 * dvcp::kFbSumRow * 8);
+}
+
+extern "C" int64_t dvcp_feature_propagation_bn_stats_workspace_bytes(int B, int N1) {
+  if (B < 0 || N1 < 0) return -1;
+  const int64_t tiles = dvcp::fb_tiles(B, N1);
+  return tiles == 0 ? 0 : fb_sum_bytes(tiles);
+}
+
+extern "C" int dvcp_feature_propagation_bn_stats(
+    const float* xyz1, int64_t x1b, int64_t x1c, int64_t x1n, int N1, const float* xyz2, int64_t x2b, int64_t x2c,
+    int64_t x2n, int N2, int B, const float* p1, int64_t p1b, int64_t p1d, int64_t p1n, int D1, const float* p2,
+    int64_t p2b, int64_t p2n, int D2, int nlayer, const int* chans, const int* relu, const float* params, int layer,
+    void* workspace, int64_t ws_bytes, double* sums, void* stream) {
+  const char* who = "dvcp_feature_propagation_bn_stats";
+  dvcp::FpLayers lay{};
+  if (int e = fb_bn_layers(who, N1, N2, B, D1, D2, nlayer, chans, relu, &lay)) return e;
+  DVCP_REQUIRE(params && sums, "%s: null pointer", who);
+  DVCP_REQUIRE(layer >= 1 && layer <= nlayer, "%s: layer %d of %d", who, layer, nlayer);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int co = chans[layer];
+  const int64_t tiles = dvcp::fb_tiles(B, N1);
+  if (tiles == 0) {
+    if (hipMemsetAsync(sums, 0, 2 * co * sizeof(double), st) != hipSuccess)
+      return dvcp::launch_status("dvcp_feature_propagation_bn_stats(empty)");
+    return DVCP_OK;
+  }
+  DVCP_REQUIRE(xyz1 && xyz2 && p2 && (D1 == 0 || p1) && workspace, "%s: null pointer", who);
+  const int64_t need = fb_sum_bytes(tiles);
+  DVCP_REQUIRE(ws_bytes >= need, "%s: workspace of %lld bytes is short of %lld", who, static_cast<long long>(ws_bytes),
+               static_cast<long long>(need));
+  const int grid = dvcp::fb_grid(tiles);
+  double* sp = static_cast<double*>(workspace);
+  hipLaunchKernelGGL(dvcp::fp_bwd_kernel<dvcp::kFbStats>, dim3(grid), dim3(dvcp::kFpThreads), 0, st,
+                     dvcp::PointsView<float>{xyz1, x1b, x1c, x1n}, N1, dvcp::PointsView<float>{xyz2, x2b, x2c, x2n}, N2,
+                     B, p1, p1b, p1d, p1n, D1, p2, p2b, p2n, D2, lay, params, nullptr, nullptr, nullptr, nullptr,
+                     nullptr, 0, nullptr, nullptr, layer, sp);
+  if (int e = dvcp::launch_status(who)) return e;
+  hipLaunchKernelGGL(dvcp::fb_fold_sums_kernel, dim3(1), dim3(128), 0, st, sp, grid * 4, co, sums);
+  return dvcp::launch_status("dvcp_feature_propagation_bn_stats(sum)");
+}
+
+extern "C" int64_t dvcp_feature_propagation_bn_backward_workspace_bytes(int B, int N1, int N2, int D2, int nlayer,
+                                                                        const int* chans, int want_p2) {
+  const int64_t need = dvcp_feature_propagation_backward_workspace_bytes(B, N1, N2, D2, nlayer, chans, want_p2);
+  if (need <= 0) return need;
+  return need + fb_sum_bytes(dvcp::fb_tiles(B, N1));
+}
+
+extern "C" int dvcp_feature_propagation_bn_backward(
+    const float* xyz1, int64_t x1b, int64_t x1c, int64_t x1n, int N1, const float* xyz2, int64_t x2b, int64_t x2c,
+    int64_t x2n, int N2, int B, const float* p1, int64_t p1b, int64_t p1d, int64_t p1n, int D1, const float* p2,
+    int64_t p2b, int64_t p2n, int D2, int nlayer, const int* chans, const int* relu, const float* params,
+    const double* bnstat, const float* grad_out, int mode, float* grad_p1, float* grad_p2, void* workspace,
+    int64_t ws_bytes, double* sums, float* grad_params, void* stream) {
+  const char* who = "dvcp_feature_propagation_bn_backward";
+  dvcp::FpLayers lay{};
+  if (int e = fb_bn_layers(who, N1, N2, B, D1, D2, nlayer, chans, relu, &lay)) return e;
+  DVCP_REQUIRE(mode >= 0 && mode <= nlayer, "%s: mode %d of %d", who, mode, nlayer);
+  DVCP_REQUIRE(params && bnstat && (mode == 0 ? grad_params != nullptr : sums != nullptr), "%s: null pointer", who);
+  if (mode != 0) grad_p1 = grad_p2 = nullptr;
+  DVCP_REQUIRE(!grad_p2 || D2 == 32 || D2 == 64, "%s: grad_p2 with D2=%d (segment_sum takes 32 or 64 columns)", who,
+               D2);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int np = dvcp::fb_nparams(nlayer, chans);
+  const int64_t tiles = dvcp::fb_tiles(B, N1);
+  if (tiles == 0) {
+    bool ok = true;
+    if (mode != 0) {
+      ok = hipMemsetAsync(sums, 0, 2 * chans[mode] * sizeof(double), st) == hipSuccess;
+    } else {
+      ok = hipMemsetAsync(grad_params, 0, static_cast<size_t>(np) * 4, st) == hipSuccess &&
+           (!grad_p2 || B == 0 ||
+            hipMemsetAsync(grad_p2, 0, static_cast<size_t>(B) * N2 * D2 * 4, st) == hipSuccess);
+    }
+    return ok ? DVCP_OK : dvcp::launch_status("dvcp_feature_propagation_bn_backward(empty)");
+  }
+  DVCP_REQUIRE(xyz1 && xyz2 && p2 && (D1 == 0 || p1) && grad_out && workspace, "%s: null pointer", who);
+  const int64_t need =
+      dvcp_feature_propagation_bn_backward_workspace_bytes(B, N1, N2, D2, nlayer, chans, grad_p2 != nullptr);
+  DVCP_REQUIRE(need >= 0, "%s: workspace size query failed", who);
+  DVCP_REQUIRE(ws_bytes >= need, "%s: workspace of %lld bytes is short of %lld", who, static_cast<long long>(ws_bytes),
+               static_cast<long long>(need));
+  const int grid = dvcp::fb_grid(tiles);
+  const int64_t E = static_cast<int64_t>(B) * N1 * 3;
+  char* w = static_cast<char*>(workspace);
+  double* sp = reinterpret_cast<double*>(w);
+  w += fb_sum_bytes(tiles);
+  float* partial = reinterpret_cast<float*>(w);
+  w += dvcp::fb_align(static_cast<int64_t>(grid) * np * 4);
+  uint32_t* keys = nullptr;
+  float* contrib = nullptr;
+  if (grad_p2) {
+    keys = reinterpret_cast<uint32_t*>(w);
+    w += dvcp::fb_align(E * 4);
+    contrib = reinterpret_cast<float*>(w);
+    w += dvcp::fb_align(E * D2 * 4);
+  }
+  const dvcp::PointsView<float> v1{xyz1, x1b, x1c, x1n}, v2{xyz2, x2b, x2c, x2n};
+  if (mode != 0) {
+    hipLaunchKernelGGL(dvcp::fp_bwd_kernel<dvcp::kFbSums>, dim3(grid), dim3(dvcp::kFpThreads), 0, st, v1, N1, v2, N2, B,
+                       p1, p1b, p1d, p1n, D1, p2, p2b, p2n, D2, lay, params, nullptr, grad_out, nullptr, nullptr,
+                       nullptr, np, nullptr, bnstat, mode, sp);
+    if (int e = dvcp::launch_status(who)) return e;
+    hipLaunchKernelGGL(dvcp::fb_fold_sums_kernel, dim3(1), dim3(128), 0, st, sp, grid * 4, chans[mode], sums);
+    return dvcp::launch_status("dvcp_feature_propagation_bn_backward(sum)");
+  }
+  hipLaunchKernelGGL(dvcp::fp_bwd_kernel<dvcp::kFbGrad>, dim3(grid), dim3(dvcp::kFpThreads), 0, st, v1, N1, v2, N2, B,
+                     p1, p1b, p1d, p1n, D1, p2, p2b, p2n, D2, lay, params, nullptr, grad_out, grad_p1, keys, contrib,
+                     np, partial, bnstat, 0, nullptr);
+  if (int e = dvcp::launch_status(who)) return e;
+  hipLaunchKernelGGL(dvcp::fe_fold_partials_kernel, dim3(dvcp::ceil_div(np, 256)), dim3(256), 0, st, partial, grid, np,
+                     grad_params);
+  if (int e = dvcp::launch_status("dvcp_feature_propagation_bn_backward(fold)")) return e;
   if (grad_p2) return dvcp::segment_sum(keys, contrib, E, static_cast<int64_t>(B) * N2, D2, grad_p2, w, st);
   return DVCP_OK;
 }

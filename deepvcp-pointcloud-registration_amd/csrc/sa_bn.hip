@@ -837,12 +837,26 @@ static int64_t bn_pack_floats(int nlayer, const int* chans) {
 
 }  // namespace dvcp
 
-// The REF-R tables (deep_feat_extraction.py:10-13 + R1): sa1 without / with normals, sa2, sa3.
+// The REF-R tables (deep_feat_extraction.py:10-13 + R1): sa1 without / with normals, sa2, sa3; then
+// the paper's sa1 (3[+3] -> 32, 32; its sa2 and sa3 are the reference's tables).
 #define DVCP_BN_TABLES(X) \
   X(0, 16, 16, 32)        \
   X(3, 16, 16, 32)        \
   X(32, 32, 64, 0)        \
-  X(64, 64, 64, 0)
+  X(64, 64, 64, 0)        \
+  X(0, 32, 32, 0)         \
+  X(3, 32, 32, 0)
+
+// Whether dvcp_sa_bn_stats / _zrows / _backward take this table (the same list they dispatch on).
+extern "C" int dvcp_sa_bn_supported(int nlayer, const int* chans) {
+  if (!chans || (nlayer != 2 && nlayer != 3)) return 0;
+  const int D = chans[0] - 3;
+#define DVCP_BN_Q(DD, A1, A2, A3) \
+  if (D == DD && chans[1] == A1 && chans[2] == A2 && (nlayer == 2 ? 0 : chans[3]) == A3) return 1;
+  DVCP_BN_TABLES(DVCP_BN_Q)
+#undef DVCP_BN_Q
+  return 0;
+}
 
 extern "C" int64_t dvcp_sa_bn_workspace_bytes(int B, int S, int nlayer, const int* chans) {
   if (B < 0 || S < 0 || !chans || (nlayer != 2 && nlayer != 3)) return -1;

@@ -68,8 +68,15 @@ SIGNATURES = {
     "dvcp_cpg1d": [_P, _P, _P, _I, _I, _P, _P, _P, _P],
     "dvcp_cpg1d_backward": [_P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _L, _P, _P],
     "dvcp_weighting_backward": [_P, _I, _P, _P, _P, _P, _L, _P, _P],
+    "dvcp_weighting_bn_stats": [_P, _I, _P, _I, _P, _L, _P, _P],
+    "dvcp_weighting_bn_forward": [_P, _I, _P, _P, _P],
+    "dvcp_weighting_bn_backward": [_P, _I, _P, _P, _P, _I, _P, _P, _L, _P, _P, _P],
     "dvcp_feature_propagation_backward": [_P, _L, _L, _L, _I, _P, _L, _L, _L, _I, _I, _P, _L, _L, _L, _I, _P, _L, _L,
                                           _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P, _P],
+    "dvcp_feature_propagation_bn_stats": [_P, _L, _L, _L, _I, _P, _L, _L, _L, _I, _I, _P, _L, _L, _L, _I, _P, _L, _L, _I,
+                                          _I, _P, _P, _P, _I, _P, _L, _P, _P],
+    "dvcp_feature_propagation_bn_backward": [_P, _L, _L, _L, _I, _P, _L, _L, _L, _I, _I, _P, _L, _L, _L, _I, _P, _L, _L,
+                                             _I, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P, _L, _P, _P, _P],
     "dvcp_group_rows_backward": [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _L, _P],
     "dvcp_svd_optimization": [_P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P],
     "dvcp_deepvcp_loss": [_P, _P, _P, _P, _I, _I, _D, _P, _P, _P, _P, _P],
@@ -160,9 +167,24 @@ def load():
     lib.dvcp_cpg1d_backward_workspace_bytes.argtypes = [ctypes.c_int]
     lib.dvcp_weighting_backward_workspace_bytes.restype = ctypes.c_int64
     lib.dvcp_weighting_backward_workspace_bytes.argtypes = [ctypes.c_int]
+    lib.dvcp_weighting_bn_nparams.restype = ctypes.c_int
+    lib.dvcp_weighting_bn_nparams.argtypes = []
+    lib.dvcp_weighting_bn_stats_workspace_bytes.restype = ctypes.c_int64
+    lib.dvcp_weighting_bn_stats_workspace_bytes.argtypes = [ctypes.c_int]
+    lib.dvcp_weighting_bn_backward_workspace_bytes.restype = ctypes.c_int64
+    lib.dvcp_weighting_bn_backward_workspace_bytes.argtypes = [ctypes.c_int]
+    lib.dvcp_weighting_bn_forward_workspace_bytes.restype = ctypes.c_int64
+    lib.dvcp_weighting_bn_forward_workspace_bytes.argtypes = [ctypes.c_int]
+    lib.dvcp_sa_bn_supported.restype = ctypes.c_int
+    lib.dvcp_sa_bn_supported.argtypes = [ctypes.c_int, ctypes.c_void_p]
     lib.dvcp_feature_propagation_backward_workspace_bytes.restype = ctypes.c_int64
     lib.dvcp_feature_propagation_backward_workspace_bytes.argtypes = [ctypes.c_int] * 5 + [ctypes.c_void_p,
                                                                                            ctypes.c_int]
+    lib.dvcp_feature_propagation_bn_stats_workspace_bytes.restype = ctypes.c_int64
+    lib.dvcp_feature_propagation_bn_stats_workspace_bytes.argtypes = [ctypes.c_int] * 2
+    lib.dvcp_feature_propagation_bn_backward_workspace_bytes.restype = ctypes.c_int64
+    lib.dvcp_feature_propagation_bn_backward_workspace_bytes.argtypes = [ctypes.c_int] * 5 + [ctypes.c_void_p,
+                                                                                              ctypes.c_int]
     lib.dvcp_group_rows_backward_workspace_bytes.restype = ctypes.c_int64
     lib.dvcp_group_rows_backward_workspace_bytes.argtypes = [ctypes.c_int] * 4
     lib.dvcp_sa_bn_pack_floats.restype = ctypes.c_int64
@@ -196,7 +218,11 @@ def exported_symbols():
             "dvcp_cpg_tiled_backward_workspace_bytes", "dvcp_src_keypoints_workspace_bytes",
             "dvcp_cpg1d_backward_workspace_bytes", "dvcp_weighting_backward_workspace_bytes",
             "dvcp_feature_propagation_backward_workspace_bytes",
-            "dvcp_group_rows_backward_workspace_bytes"] + list(SIGNATURES)
+            "dvcp_group_rows_backward_workspace_bytes", "dvcp_weighting_bn_nparams",
+            "dvcp_weighting_bn_stats_workspace_bytes", "dvcp_weighting_bn_backward_workspace_bytes",
+            "dvcp_weighting_bn_forward_workspace_bytes", "dvcp_sa_bn_supported",
+            "dvcp_feature_propagation_bn_stats_workspace_bytes",
+            "dvcp_feature_propagation_bn_backward_workspace_bytes"] + list(SIGNATURES)
 
 
 # When a list, every entry-point call appends (name, start_event, end_event, work) recorded on

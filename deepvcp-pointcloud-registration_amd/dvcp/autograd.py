@@ -27,6 +27,8 @@ Paper mode (dvcp/paper.py, not reference parity) adds the two links its stage he
   * ``cpg1d``      -- the second stage's 1-D CPG (dvcp_cpg1d / dvcp_cpg1d_backward);
   * ``weighting``  -- the paper's weighting layer (dvcp_weighting / dvcp_weighting_backward), whose
                       scores are the pose solve's weights there and so do carry a gradient;
+  * ``weighting_bn`` -- the same layer in training mode, batch-statistics BN (dvcp_weighting_bn_stats /
+                      _forward / _backward through dvcp/batchnorm.py);
 
 and the links that train its extractor (``DeepVCPPaper(train_extractor=True)``):
 
@@ -151,6 +153,26 @@ class _Weighting(torch.autograd.Function):
         gp, gfeat = ops.weighting_backward(rows, params, g, want_feat=want_feat)
         return (gfeat.to(ctx.dtypes[0]) if want_feat else None,
                 gp.to(ctx.dtypes[1]) if ctx.needs_input_grad[1] else None)
+
+
+class _WeightingBN(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, wl, feat, *params):
+        rows = feat.contiguous().float()
+        score, st = batchnorm.weighting_train_forward(wl, rows)
+        ctx.save_for_backward(st["rows"], st["pack"], st["bnstat"])
+        ctx.wl, ctx.M, ctx.dtypes = wl, st["M"], (feat.dtype, [p.dtype for p in params])
+        return score
+
+    @staticmethod
+    def backward(ctx, g):
+        want_feat = ctx.needs_input_grad[1]
+        rows, pack, bnstat = ctx.saved_tensors
+        st = dict(rows=rows, pack=pack, bnstat=bnstat, M=ctx.M)
+        grads, gfeat = batchnorm.weighting_train_backward(ctx.wl, st, g, want_feat)
+        return (None, gfeat.to(ctx.dtypes[0]) if want_feat else None,
+                *[gr.to(dt) if ctx.needs_input_grad[2 + k] else None
+                  for k, (gr, dt) in enumerate(zip(grads, ctx.dtypes[1]))])
 
 
 class _SrcKeypoints(torch.autograd.Function):
@@ -331,6 +353,17 @@ def weighting(feat, weighting_module):
     return _Weighting.apply(feat, weighting_module.folded_params())
 
 
+def weighting_bn(feat, weighting_module):
+    """The paper's weighting layer in training mode (batch-statistics BN; dvcp/batchnorm.py
+    ``weighting_train_forward`` / ``weighting_train_backward``, dvcp_weighting_bn_*) on rows (P, 32),
+    differentiable in the rows and in fc1-3 and bn1-2's weights and biases.  The forward updates the
+    running statistics once; a frozen parameter gets no gradient, but the layer still normalises with the
+    batch's statistics."""
+    m = weighting_module
+    params = [t for lin, bn in ((m.fc1, m.bn1), (m.fc2, m.bn2)) for t in (lin.weight, lin.bias, bn.weight, bn.bias)]
+    return _WeightingBN.apply(m, feat, *params, m.fc3.weight, m.fc3.bias)
+
+
 def src_keypoints(fe_xyz, fe_feat, topk_idx, kstart, R_init, radius=1.0, nsample=32):
     """The key-point stage (deepVCP.py:39-68 + get_cat_feat_src.py), differentiable in fe_feat
     through the index_points gather (pointnet2_utils.py:59) and the distance weighting."""
@@ -398,6 +431,38 @@ class _FeatureProp(torch.autograd.Function):
         return (None, None, None, None, gp1, gp2, *_wanted(ctx, 6, grads, [dt for _, dt in ctx.shapes]))
 
 
+class _FeaturePropBN(torch.autograd.Function):
+    """_FeatureProp with ``fp`` in training mode: batchnorm.fp_train_forward (statistics passes, running
+    statistics updated, then the forward kernel) and fp_train_backward."""
+
+    @staticmethod
+    def forward(ctx, fp, fc, xyz1, xyz2, p1, p2_rows, *params):
+        p2 = p2_rows.detach()
+        out, st = batchnorm.fp_train_forward(fp, xyz1, xyz2, p1, p2, fc)
+        ctx.save_for_backward(xyz1, xyz2, p1, p2, st["pack"], st["bnstat"])
+        ctx.st = {k: st[k] for k in ("M", "chans", "relu", "nbn")}
+        ctx.shapes = [(p.shape, p.dtype) for p in params]
+        ctx.in_dtypes = (None if p1 is None else p1.dtype, p2_rows.dtype)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        xyz1, xyz2, p1, p2, pack, bnstat = ctx.saved_tensors
+        st = dict(ctx.st, pack=pack, bnstat=bnstat)
+        want_p1 = p1 is not None and ctx.needs_input_grad[4]
+        want_p2 = ctx.needs_input_grad[5]
+        gp, gp1, gp2 = batchnorm.fp_train_backward(st, xyz1, xyz2, p1, p2, g, want_p1=want_p1, want_p2=want_p2)
+        nconv, chans = st["nbn"], st["chans"]
+        wshapes = [ctx.shapes[4 * l][0] for l in range(nconv)] + [ctx.shapes[-2][0]]
+        per = _layer_grads(gp, chans, wshapes)
+        grads = per[:4 * nconv]
+        if len(chans) - 1 > nconv:      # the fused fc: its dgamma / dbeta are discarded
+            grads += per[4 * nconv:4 * nconv + 2]
+        gp1 = gp1.permute(0, 2, 1).to(ctx.in_dtypes[0]) if want_p1 else None
+        gp2 = gp2.to(ctx.in_dtypes[1]) if want_p2 else None
+        return (None, None, None, None, gp1, gp2, *_wanted(ctx, 6, grads, [dt for _, dt in ctx.shapes]))
+
+
 def _fp_tensors(fp, fc=None):
     out = []
     for conv, bn in zip(fp.mlp_convs, fp.mlp_bns):
@@ -410,8 +475,11 @@ def feature_propagation(fp, xyz1, xyz2, p1, p2_rows, fc=None):
     bits) -> (B, N1, C) rows, differentiable in p1 (B, D1, N1), p2_rows (B, N2, D2), the layers' conv and
     BN weights and biases and the optional fused ``fc`` (backward: dvcp_feature_propagation_backward).
     The eval-mode BN is folded as for the SA layers: the packed dgamma / dbeta are bn.weight's /
-    bn.bias' gradients, the running statistics are fixed."""
-    return _FeatureProp.apply(fp, fc, xyz1, xyz2, p1, p2_rows, *_fp_tensors(fp, fc))
+    bn.bias' gradients, the running statistics are fixed.  With ``fp`` built with ``bn_train=True`` and in
+    training mode: batch statistics (dvcp_feature_propagation_bn_stats / _bn_backward through
+    dvcp/batchnorm.py), the running statistics updated once per call."""
+    fn = _FeaturePropBN if (getattr(fp, "bn_train", False) and fp.training) else _FeatureProp
+    return fn.apply(fp, fc, xyz1, xyz2, p1, p2_rows, *_fp_tensors(fp, fc))
 
 
 class _GroupRows(torch.autograd.Function):
@@ -459,6 +527,29 @@ class _SaGroupMlp(torch.autograd.Function):
         return (None, None, None, gF, None, None, None, *_wanted(ctx, 7, grads, [dt for _, dt in ctx.shapes]))
 
 
+class _SaGroupMlpBN(torch.autograd.Function):
+    """_SaGroupMlp with ``sa`` in training mode: batchnorm.train_forward (batch statistics, running
+    statistics updated; the z rows kept when a backward will run) and train_backward."""
+
+    @staticmethod
+    def forward(ctx, sa, xyz, ctr, feat, count, lst, ns, *params):
+        out, st = batchnorm.train_forward(sa, xyz, ctr, feat, count, lst, ns, keep_zrows=any(ctx.needs_input_grad))
+        ctx.sa = sa
+        ctx.lay = dict(pts=xyz, ctr=ctr, feat=feat, count=count, lst=lst, ns=int(ns), bn=st)
+        ctx.shapes = [(p.shape, p.dtype) for p in params]
+        ctx.feat_dtype = None if feat is None else feat.dtype
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        want_feat = ctx.lay["feat"] is not None and ctx.needs_input_grad[3]
+        gp, gF = batchnorm.train_backward(ctx.sa, ctx.lay, g, want_feat_grad=want_feat)
+        ctx.lay = None
+        grads = _layer_grads(gp, ctx.sa.chans, [ctx.shapes[4 * l][0] for l in range(len(ctx.sa.chans) - 1)])
+        gF = gF.permute(0, 2, 1).to(ctx.feat_dtype) if want_feat else None
+        return (None, None, None, gF, None, None, None, *_wanted(ctx, 7, grads, [dt for _, dt in ctx.shapes]))
+
+
 def paper_feat_extraction(fe, pts, starts):
     """``PaperFeatExtraction.forward`` (pts (B, C, N), starts (3, B)) -> (B, N, 32), the same kernels and
     bits, differentiable in every parameter of ``fe``.  FPS and the ball queries run as in inference
@@ -466,7 +557,9 @@ def paper_feat_extraction(fe, pts, starts):
     propagation with dvcp_feature_propagation_backward; torch adds a level's two consumers (f1: fp2's
     d p1 + sa2's feature gradient; f2: fp3's + sa3's).  Saved for backward: per level the coordinates,
     centres, counts, lists and feature rows.  The SA backward's feature scatter uses float atomics, so
-    gradients upstream of it (sa1, sa2) are not bit-reproducible."""
+    gradients upstream of it (sa1, sa2) are not bit-reproducible.  With ``fe`` built with ``bn_train=True``
+    a module in training mode takes its batch-statistics pair instead (batchnorm.train_forward /
+    train_backward for a set abstraction, fp_train_forward / fp_train_backward for a propagation)."""
     B, _, N = pts.shape
     xyz = pts[:, :3, :]
     feat = pts[:, 3:, :] if fe.use_normal else None
@@ -477,7 +570,9 @@ def paper_feat_extraction(fe, pts, starts):
             _, c = ops.fps(pxyz, sa.npoint, st.to(pts.device), pdim=2)
             ns = min(int(sa.nsample), pxyz.shape[2])
             count, lst, _ = ops.ball_query(pxyz, c, sa.radius, ns, pdim=2, cdim_pts=2)
-        rows = _SaGroupMlp.apply(sa, pxyz, c, pf, count, lst, ns,
+        # each module follows its own .training (fe built with bn_train=True): batch statistics, or today's
+        fn = _SaGroupMlpBN if (getattr(fe, "bn_train", False) and sa.training) else _SaGroupMlp
+        rows = fn.apply(sa, pxyz, c, pf, count, lst, ns,
                                  *[t for conv, bn in zip(sa.mlp_convs, sa.mlp_bns)
                                    for t in (conv.weight, conv.bias, bn.weight, bn.bias)])
         levels.append((c, rows.permute(0, 2, 1)))

@@ -24,6 +24,11 @@ whose mean terms make every entry's gradient non-zero: sums of the top layer ove
 the per-entry rows of the weight gradients and the feature gradient (dvcp_sa_bn_backward modes
 L..1, 0; csrc/sa_bn.hip); dW_l, db_l are then GEMMs over the entries (hipBLASLt via torch.bmm
 over the rows' 65536-entry chunks, chunk sums in fp64).
+
+Paper mode (dvcp/paper.py, ``bn_train=True``): the paper's sa1 table (3[+3]-32-32) takes the
+lane-per-entry passes above; the feature propagations and the weighting layer have their own pairs at
+the end of this file (``fp_train_forward`` / ``fp_train_backward``, csrc/paper_fe_bwd.hip's template
+modes; ``weighting_train_forward`` / ``weighting_train_backward``, csrc/paper_wl_bn.hip).
 """
 import torch
 
@@ -198,3 +203,145 @@ def _gemm_nt(a, b):
     (hipBLASLt via torch.bmm, B transposed by strides, no copy), the chunk products summed in fp64
     in a fixed order."""
     return torch.bmm(a, b.transpose(1, 2)).double().sum(0)
+
+
+# ---- paper mode: feature propagation (dvcp.paper.PointNetFeaturePropagation, csrc/paper_fe_bwd.hip) ----
+def fp_train_forward(fp, xyz1, xyz2, p1, p2_rows, fc=None):
+    """``fp`` (Conv1d 1x1 + BN1d + ReLU per layer, optionally the fused ``fc`` as a plain last layer) in
+    training mode: one statistics pass per BN layer (dvcp_feature_propagation_bn_stats, the layers below
+    normalised by their batch statistics), mean / biased variance folded with gamma, beta into scale |
+    shift in fp64 and rounded once, the running statistics updated, then the existing forward kernel on
+    the finished pack: the train-mode forward adds no kernel.  Returns ((B, N1, C) rows, state for
+    ``fp_train_backward``).  B N1 = 0: the rows are empty and nothing is updated."""
+    B, N1 = xyz1.shape[0], xyz1.shape[2]
+    M = B * N1
+    require_batch(M, (B, fp.chans[0], N1))
+    dev = xyz1.device
+    chans = fp.chans + ([fc.weight.shape[0]] if fc is not None else [])
+    relu = [1] * len(fp.mlp_convs) + ([0] if fc is not None else [])
+    with torch.no_grad():
+        parts, offs, o = [], [], 0
+        for lin in list(fp.mlp_convs) + ([fc] if fc is not None else []):
+            co, ci = lin.weight.shape[0], lin.weight.shape[1]
+            parts += [lin.weight.reshape(-1).float(), lin.bias.float(), torch.ones(co, device=dev),
+                      torch.zeros(co, device=dev)]
+            offs.append((o, ci, co))
+            o += ci * co + 3 * co
+        pack = torch.cat(parts).contiguous()
+        bnstat = torch.zeros(4 * sum(chans[1:]), dtype=torch.float64, device=dev)
+        so = 0
+        for layer, (o, ci, co) in enumerate(offs, 1):
+            if layer > len(fp.mlp_bns):          # the fused fc: mean 0, rstd 1, no mean terms
+                bnstat[so + co:so + 2 * co] = 1.0
+            elif M:
+                bn = fp.mlp_bns[layer - 1]
+                sums = ops.feature_propagation_bn_stats(xyz1, xyz2, p2_rows, p1, chans, relu, pack, layer)
+                mean = sums[0] / M
+                var = (sums[1] / M - mean * mean).clamp_min(0.0)
+                rstd = torch.rsqrt(var + bn.eps)
+                scale = bn.weight.double() * rstd
+                shift = bn.bias.double() - mean * scale
+                v = o + co * ci + co
+                pack[v:v + 2 * co] = torch.cat([scale, shift]).float()
+                bnstat[so:so + 2 * co] = torch.cat([mean, rstd])
+                _update_running(bn, mean, var, M)
+            so += 4 * co
+        if M:
+            out = ops.feature_propagation(xyz1, xyz2, p2_rows, p1, chans, relu, pack)
+        else:
+            out = torch.empty(B, N1, chans[-1], dtype=torch.float32, device=dev)
+    return out, dict(pack=pack, bnstat=bnstat, M=M, chans=chans, relu=relu, nbn=len(fp.mlp_bns))
+
+
+def fp_train_backward(st, xyz1, xyz2, p1, p2_rows, g, want_p1=True, want_p2=True):
+    """Backward of ``fp_train_forward`` on its operands: (packed parameter gradient, per layer dW | db |
+    dgamma | dbeta with dgamma = B and dbeta = A of the sums passes; d p1 (B, N1, D1) or None; d p2_rows
+    (B, N2, D2) or None).  The top BN layer's sums first (dvcp_feature_propagation_bn_backward mode nbn),
+    one pass per lower layer, then the gradient pass (mode 0)."""
+    chans, relu, M = st["chans"], st["relu"], st["M"]
+    bnstat = st["bnstat"].clone()
+    args = (xyz1, xyz2, p2_rows, p1, chans, relu, st["pack"])
+    so = [4 * sum(chans[1:l]) for l in range(1, len(chans))]
+    sums = {}
+    for k in range(st["nbn"], 0, -1):
+        co = chans[k]
+        sums[k] = ops.feature_propagation_bn_backward(*args, bnstat, g, k)
+        if M:
+            bnstat[so[k - 1] + 2 * co:so[k - 1] + 4 * co] = (sums[k] / M).reshape(-1)
+    gp, gp1, gp2 = ops.feature_propagation_bn_backward(*args, bnstat, g, 0, want_p1=want_p1, want_p2=want_p2)
+    o = 0
+    for k, (ci, co) in enumerate(zip(chans[:-1], chans[1:]), 1):
+        if k in sums:
+            gp[o + ci * co + co:o + ci * co + 3 * co] = torch.cat([sums[k][1], sums[k][0]]).float()
+        o += ci * co + 3 * co
+    return gp, gp1, gp2
+
+
+# ---- paper mode: the weighting layer (dvcp.paper.PaperWeighting, csrc/paper_wl_bn.hip) -------------
+# (offset, C_in, C_out) of fc1 / fc2 in the train-mode pack W | b | scale | shift, then fc3, and the
+# offset of each BN layer's mean | rstd | A/M | B/M in the statistics vector
+_WL_LAYERS = ((0, 32, 16), (32 * 16 + 3 * 16, 16, 8))
+_WL_STAT = (0, 4 * 16)
+
+
+def require_batch(M, shape):
+    """torch's refusal of batch statistics over a single value per channel."""
+    if M == 1:
+        raise ValueError(f"Expected more than 1 value per channel when training, got input size {tuple(shape)}")
+
+
+def weighting_train_forward(wl, rows):
+    """The paper's weighting layer (Sec. 3.2) with ``wl`` in training mode on rows (P, 32) fp32: one
+    statistics pass per BN layer (dvcp_weighting_bn_stats: fp64 sums of z and z^2, the layer below
+    normalised by its batch statistics), mean / biased variance folded into scale | shift in fp64 and
+    rounded once, the running statistics updated (once per call), then the scores
+    (dvcp_weighting_bn_forward).  Returns (scores (P,), state for ``weighting_train_backward``).  P = 0:
+    no scores, no update."""
+    P = rows.shape[0]
+    require_batch(P, rows.shape)
+    dev = rows.device
+    with torch.no_grad():
+        parts = []
+        for lin in (wl.fc1, wl.fc2):
+            c = lin.weight.shape[0]
+            parts += [lin.weight.reshape(-1).float(), lin.bias.float(), torch.ones(c, device=dev),
+                      torch.zeros(c, device=dev)]
+        pack = torch.cat(parts + [wl.fc3.weight.reshape(-1).float(), wl.fc3.bias.float()]).contiguous()
+        bnstat = torch.zeros(ops.WEIGHTING_BN_NSTAT, dtype=torch.float64, device=dev)
+        if P == 0:
+            return torch.empty(0, dtype=torch.float32, device=dev), dict(pack=pack, bnstat=bnstat, M=0, rows=rows)
+        for layer, (bn, (o, cin, cout), so) in enumerate(zip((wl.bn1, wl.bn2), _WL_LAYERS, _WL_STAT), 1):
+            sums = ops.weighting_bn_stats(rows, pack, layer)
+            mean = sums[0] / P
+            var = (sums[1] / P - mean * mean).clamp_min(0.0)
+            rstd = torch.rsqrt(var + bn.eps)
+            scale = bn.weight.double() * rstd
+            shift = bn.bias.double() - mean * scale
+            v = o + cout * cin + cout
+            pack[v:v + 2 * cout] = torch.cat([scale, shift]).float()
+            bnstat[so:so + 2 * cout] = torch.cat([mean, rstd])
+            _update_running(bn, mean, var, P)
+        score = ops.weighting_bn_forward(rows, pack)
+    return score, dict(pack=pack, bnstat=bnstat, M=P, rows=rows)
+
+
+def weighting_train_backward(wl, st, g, want_feat):
+    """Backward of ``weighting_train_forward``: ([d fc1.weight, d fc1.bias, d bn1.weight, d bn1.bias, d
+    fc2.weight, d fc2.bias, d bn2.weight, d bn2.bias, d fc3.weight, d fc3.bias] fp32, d rows (P, 32) or
+    None).  The top BN layer's sums first (dvcp_weighting_bn_backward mode 2), then the lower one's
+    (mode 1), then the gradient pass (mode 0); d gamma = B and d beta = A are the sums themselves."""
+    pack, M, rows = st["pack"], st["M"], st["rows"]
+    bnstat = st["bnstat"].clone()
+    sums = {}
+    if M:
+        for mode, so, c in ((2, _WL_STAT[1], 8), (1, _WL_STAT[0], 16)):
+            sums[mode] = ops.weighting_bn_backward(rows, pack, bnstat, g, mode)
+            bnstat[so + 2 * c:so + 4 * c] = (sums[mode] / M).reshape(-1)
+    else:
+        sums = {2: torch.zeros(2, 8, dtype=torch.float64, device=rows.device),
+                1: torch.zeros(2, 16, dtype=torch.float64, device=rows.device)}
+    gp, gfeat = ops.weighting_bn_backward(rows, pack, bnstat, g, 0, want_feat=want_feat)
+    w1, b1, w2, b2, w3, b3 = torch.split(gp, [16 * 32, 16, 8 * 16, 8, 8, 1])
+    grads = [w1.view(16, 32), b1, sums[1][1].float(), sums[1][0].float(),
+             w2.view(8, 16), b2, sums[2][1].float(), sums[2][0].float(), w3.view(1, 8), b3]
+    return grads, gfeat

@@ -866,6 +866,12 @@ def sa_bn_pack_floats(chans):
     return int(_lib.load().dvcp_sa_bn_pack_floats(len(chans) - 1, ch.data_ptr()))
 
 
+def sa_bn_supported(chans):
+    """Whether the batch-statistics passes (dvcp_sa_bn_stats / _zrows / _backward) take this table."""
+    ch = torch.tensor(list(chans), dtype=torch.int32)
+    return bool(_lib.load().dvcp_sa_bn_supported(len(chans) - 1, ch.data_ptr()))
+
+
 def sa_bn_stats(xyz, ctr, feat, count, lst, nsample, chans, pack, layer, xyz_pdim=2, feat_ddim=1, feat_pdim=2,
                 want_zrows=False):
     """Training-mode BatchNorm statistics of the grouped MLP (pointnet2_utils.py:198 in train()):
@@ -1206,6 +1212,71 @@ def weighting_backward(feat, params, grad_score, want_feat=True):
     return gp, gfeat
 
 
+WEIGHTING_BN_NPARAMS = WEIGHTING_NPARAMS + 2 * (16 + 8)   # W | b | scale | shift per BN layer, then fc3
+WEIGHTING_BN_NSTAT = 4 * (16 + 8)                         # mean | rstd | A/M | B/M per BN layer
+
+
+def _wbn_rows(who, feat, params):
+    _lib.require_gpu(feat, params)
+    if feat.dim() != 2 or feat.shape[1] != 32 or feat.dtype != torch.float32 or not feat.is_contiguous():
+        raise RuntimeError(f"{who}: feat must be contiguous (P, 32) fp32, got {tuple(feat.shape)}")
+    if params.numel() != WEIGHTING_BN_NPARAMS or params.dtype != torch.float32 or not params.is_contiguous():
+        raise RuntimeError(f"{who}: expected {WEIGHTING_BN_NPARAMS} contiguous fp32 parameters, got {params.numel()}")
+    return feat.shape[0]
+
+
+def weighting_bn_stats(feat, params, layer):
+    """Batch statistics of the paper's weighting layer in training mode: (2, C) fp64 = per-channel sum z
+    and sum z^2 of fc``layer``'s output (1: C = 16, 2: C = 8) over the P rows, the layer below
+    normalised by the scale | shift in ``params`` (the train-mode pack, WEIGHTING_BN_NPARAMS)."""
+    P = _wbn_rows("weighting_bn_stats", feat, params)
+    C = {1: 16, 2: 8}[int(layer)]
+    sums = torch.empty(2, C, dtype=torch.float64, device=feat.device)
+    ws = _workspace(_lib.load().dvcp_weighting_bn_stats_workspace_bytes(P), feat.device)
+    macs = (32 * 16 + (16 * 8 if layer == 2 else 0)) * P
+    call("dvcp_weighting_bn_stats", ptr(feat), P, ptr(params), int(layer), ptr(ws), ws.numel() * 4, ptr(sums),
+         stream(), work=(2.0 * macs, 4.0 * P * 32))
+    return sums
+
+
+def weighting_bn_forward(feat, params):
+    """The paper's weighting layer with the BN layers as (W x + b) * scale + shift (no fold; the
+    train-mode pack): (P, 32) -> (P,) scores."""
+    P = _wbn_rows("weighting_bn_forward", feat, params)
+    score = torch.empty(P, dtype=torch.float32, device=feat.device)
+    call("dvcp_weighting_bn_forward", ptr(feat), P, ptr(params), ptr(score), stream(),
+         work=(2.0 * (32 * 16 + 16 * 8 + 8) * P, 4.0 * P * 33))
+    return score
+
+
+def weighting_bn_backward(feat, params, bnstat, grad_score, mode, want_feat=True):
+    """Batch-statistics backward of ``weighting_bn_forward``.  ``bnstat`` (fp64): mean | rstd | A/M | B/M
+    of bn1 (4 x 16), then of bn2 (4 x 8).  mode 2, 1: (2, C) fp64 = A | B of that layer (given the layer
+    above); mode 0: (d W1 | d b1 | d W2 | d b2 | d W3 | d b3 (WEIGHTING_NPARAMS, summed in a fixed order),
+    d feat (P, 32) or None)."""
+    P = _wbn_rows("weighting_bn_backward", feat, params)
+    _lib.require_gpu(bnstat, grad_score)
+    if (bnstat.numel() != WEIGHTING_BN_NSTAT or bnstat.dtype != torch.float64 or not bnstat.is_contiguous()
+            or grad_score.numel() != P):
+        raise RuntimeError(f"weighting_bn_backward: expected {WEIGHTING_BN_NSTAT} fp64 statistics and {P} score "
+                           f"gradients, got {bnstat.numel()} and {grad_score.numel()}")
+    dev = feat.device
+    g = grad_score.reshape(P).float().contiguous()
+    ws = _workspace(_lib.load().dvcp_weighting_bn_backward_workspace_bytes(P), dev)
+    macs = (32 * 16 + 16 * 8 + 8) * P
+    if mode:
+        sums = torch.empty(2, {1: 16, 2: 8}[int(mode)], dtype=torch.float64, device=dev)
+        call("dvcp_weighting_bn_backward", ptr(feat), P, ptr(params), ptr(bnstat), ptr(g), int(mode), None, ptr(ws),
+             ws.numel() * 4, ptr(sums), None, stream(), work=(2.0 * macs * 2, 4.0 * P * 33))
+        return sums
+    gfeat = torch.empty(P, 32, dtype=torch.float32, device=dev) if want_feat else None
+    gp = torch.empty(WEIGHTING_NPARAMS, dtype=torch.float32, device=dev)
+    call("dvcp_weighting_bn_backward", ptr(feat), P, ptr(params), ptr(bnstat), ptr(g), 0, ptr(gfeat), ptr(ws),
+         ws.numel() * 4, None, ptr(gp), stream(),
+         work=(2.0 * macs * (3 if want_feat else 2), 4.0 * P * (33 + (32 if want_feat else 0))))
+    return gp, gfeat
+
+
 def fp_nparams(chans):
     """Packed size of a propagation's parameters and of their gradient: (ci co + 3 co) per layer."""
     return sum(a * b + 3 * b for a, b in zip(chans[:-1], chans[1:]))
@@ -1255,6 +1326,83 @@ def feature_propagation_backward(xyz1, xyz2, p2_rows, p1, chans, relu, params, b
          work=(B * N1 * (9.0 * N2 + 2.0 * macs * (3 if (want_p1 or want_p2) else 2)),
                4.0 * B * (3 * (N1 + N2) + N2 * D2 + N1 * (D1 + chans[-1]) + (N1 * D1 if want_p1 else 0)
                           + (N1 * 3 * D2 * 2 + N2 * D2 if want_p2 else 0))))
+    return gp, gp1, gp2
+
+
+def _fp_operands(who, xyz1, xyz2, p2_rows, p1, chans, relu):
+    """The operand list dvcp_feature_propagation and its batch-statistics passes share."""
+    B = xyz1.shape[0]
+    N1, x1b, x1c, x1n = _pts(xyz1, 2)
+    N2, x2b, x2c, x2n = _pts(xyz2, 2)
+    if p2_rows.dtype != torch.float32 or p2_rows.stride(2) != 1:
+        raise ValueError(f"{who}: p2 rows must be fp32 with contiguous channels")
+    D2 = p2_rows.shape[2]
+    if p1 is not None:
+        if p1.dtype != torch.float32:
+            p1 = p1.float()
+        D1, (p1b, p1d, p1n) = p1.shape[1], p1.stride()
+    else:
+        D1, p1b, p1d, p1n = 0, 0, 0, 0
+    ch = torch.tensor(list(chans), dtype=torch.int32)
+    rl = torch.tensor([int(bool(r)) for r in relu], dtype=torch.int32)
+    args = (ptr(xyz1), x1b, x1c, x1n, N1, ptr(xyz2), x2b, x2c, x2n, N2, B, ptr(p1), p1b, p1d, p1n, D1, ptr(p2_rows),
+            p2_rows.stride(0), p2_rows.stride(1), D2, len(chans) - 1, ptr(ch), ptr(rl))
+    return args, (B, N1, N2, D1, D2), (ch, rl, p1)   # the last tuple keeps the host arrays alive
+
+
+def feature_propagation_bn_stats(xyz1, xyz2, p2_rows, p1, chans, relu, params, layer):
+    """Batch statistics of ``feature_propagation`` in training mode: (2, chans[layer]) fp64 = per-channel
+    sum z and sum z^2 of layer ``layer``'s (1-based) conv output over the B N1 rows, the layers below
+    evaluated with the scale | shift in ``params``."""
+    _lib.require_gpu(xyz1, xyz2, p2_rows, params)
+    chans = list(chans)
+    args, (B, N1, N2, D1, D2), keep = _fp_operands("feature_propagation_bn_stats", xyz1, xyz2, p2_rows, p1, chans, relu)
+    sums = torch.empty(2, chans[layer], dtype=torch.float64, device=xyz1.device)
+    ws = _workspace(_lib.load().dvcp_feature_propagation_bn_stats_workspace_bytes(B, N1), xyz1.device)
+    macs = sum(a * b for a, b in zip(chans[:layer], chans[1:layer + 1]))
+    call("dvcp_feature_propagation_bn_stats", *args, ptr(params), int(layer), ptr(ws), ws.numel() * 4, ptr(sums),
+         stream(), work=(B * N1 * (9.0 * N2 + 2.0 * macs), 4.0 * B * (3 * (N1 + N2) + N2 * D2 + N1 * D1)))
+    return sums
+
+
+def feature_propagation_bn_backward(xyz1, xyz2, p2_rows, p1, chans, relu, params, bnstat, grad_out, mode, want_p1=True,
+                                    want_p2=True):
+    """Batch-statistics backward of ``feature_propagation``.  ``bnstat`` (fp64): per layer mean | rstd | A/M |
+    B/M (0 | 1 | 0 | 0 for a fused fc).  mode k >= 1: (2, chans[k]) fp64 = A_k | B_k, given the layers above;
+    mode 0: (d params, per layer dW | db | dgamma | dbeta; d p1 (B, N1, D1) or None; d p2_rows (B, N2, D2) or
+    None), as ``feature_propagation_backward``."""
+    _lib.require_gpu(xyz1, xyz2, p2_rows, params, bnstat, grad_out)
+    chans = list(chans)
+    args, (B, N1, N2, D1, D2), keep = _fp_operands("feature_propagation_bn_backward", xyz1, xyz2, p2_rows, p1, chans,
+                                                   relu)
+    if grad_out.numel() != B * N1 * chans[-1]:
+        raise RuntimeError(f"feature_propagation_bn_backward: grad_out {tuple(grad_out.shape)} is not "
+                           f"({B}, {N1}, {chans[-1]})")
+    if bnstat.dtype != torch.float64 or bnstat.numel() != 4 * sum(chans[1:]) or not bnstat.is_contiguous():
+        raise RuntimeError(f"feature_propagation_bn_backward: expected {4 * sum(chans[1:])} fp64 statistics, got "
+                           f"{bnstat.numel()} {bnstat.dtype}")
+    dev = xyz1.device
+    g = grad_out.reshape(B, N1, chans[-1]).float().contiguous()
+    want_p1 = bool(want_p1) and D1 > 0 and mode == 0
+    want_p2 = bool(want_p2) and mode == 0
+    nbytes = int(_lib.load().dvcp_feature_propagation_bn_backward_workspace_bytes(B, N1, N2, D2, len(chans) - 1,
+                                                                                  keep[0].data_ptr(), int(want_p2)))
+    if nbytes < 0:
+        raise RuntimeError("dvcp_feature_propagation_bn_backward_workspace_bytes: size query failed")
+    ws = _workspace(nbytes, dev)
+    macs = sum(a * b for a, b in zip(chans[:-1], chans[1:]))
+    work = (B * N1 * (9.0 * N2 + 2.0 * macs * (3 if (want_p1 or want_p2) else 2)),
+            4.0 * B * (3 * (N1 + N2) + N2 * D2 + N1 * (D1 + chans[-1])))
+    if mode:
+        sums = torch.empty(2, chans[mode], dtype=torch.float64, device=dev)
+        call("dvcp_feature_propagation_bn_backward", *args, ptr(params), ptr(bnstat), ptr(g), int(mode), None, None,
+             ptr(ws), ws.numel() * 4, ptr(sums), None, stream(), work=work)
+        return sums
+    gp = torch.empty(fp_nparams(chans), dtype=torch.float32, device=dev)
+    gp1 = torch.empty(B, N1, D1, dtype=torch.float32, device=dev) if want_p1 else None
+    gp2 = torch.empty(B, N2, D2, dtype=torch.float32, device=dev) if want_p2 else None
+    call("dvcp_feature_propagation_bn_backward", *args, ptr(params), ptr(bnstat), ptr(g), 0, ptr(gp1), ptr(gp2),
+         ptr(ws), ws.numel() * 4, None, ptr(gp), stream(), work=work)
     return gp, gp1, gp2
 
 

@@ -19,12 +19,16 @@ choices the paper leaves open.
     z line scored by a 1-D CNN (dvcp_cpg1d).  Inference by default; ``train_heads=True`` trains
     the two stages' heads (weighting layer, DFE, CPG) with the extractor frozen, and
     ``train_extractor=True`` the extractor with them (dvcp_feature_propagation_backward,
-    dvcp_group_rows_backward, dvcp_sa_group_mlp_backward).
+    dvcp_group_rows_backward, dvcp_sa_group_mlp_backward).  All of that with BatchNorm on its running
+    statistics; ``bn_train=True`` makes ``.train()`` mean what it means in torch: every module with
+    BatchNorm (the set abstractions, the propagations, ``PaperWeighting``) follows its own ``.training``
+    and, in training mode, normalises with the batch's statistics and updates its running statistics
+    (dvcp_sa_bn_*, dvcp_feature_propagation_bn_*, dvcp_weighting_bn_*; dvcp/batchnorm.py).
 """
 import torch
 import torch.nn as nn
 
-from . import _lib, autograd, ops
+from . import _lib, autograd, batchnorm, ops
 from ._params import bn_affine, cached_pack
 from .cpg import _wants_grad
 from .cpg import cpg as _cpg3d
@@ -87,11 +91,20 @@ class PointNetFeaturePropagation(nn.Module):
     forward(xyz1 (B, 3, N), xyz2 (B, 3, S), points1 (B, D1, N) or None, points2 (B, D2, S)) ->
     (B, D', N), one HIP launch (eval-mode BN folded).  In eval mode with autograd on and a parameter or
     a feature input requiring a gradient, the output carries one (``autograd.feature_propagation``:
-    the same forward kernel and bits, backward dvcp_feature_propagation_backward); training mode
-    (batch-statistics BN) is refused."""
+    the same forward kernel and bits, backward dvcp_feature_propagation_backward).
 
-    def __init__(self, in_channel, mlp):
+    ``bn_train`` (a plain attribute: no parameter or buffer).  False: training mode is refused.  True: in
+    training mode every layer normalises with the batch mean and biased variance over the B N rows and
+    updates running_mean / running_var / num_batches_tracked once per forward call (momentum, None
+    included; unbiased variance): ``batchnorm.fp_train_forward`` (one dvcp_feature_propagation_bn_stats
+    pass per layer, then the same forward kernel on the finished scale | shift), recorded by
+    ``autograd.feature_propagation`` when something requires a gradient (backward:
+    dvcp_feature_propagation_bn_backward), unrecorded otherwise, no_grad included.  B N = 1 raises
+    ValueError before any launch, as torch does.  Eval mode: the paths above, bit for bit."""
+
+    def __init__(self, in_channel, mlp, bn_train=False):
         super().__init__()
+        self.bn_train = bool(bn_train)
         self.mlp_convs = nn.ModuleList()
         self.mlp_bns = nn.ModuleList()
         last = in_channel
@@ -128,8 +141,14 @@ class PointNetFeaturePropagation(nn.Module):
         return ops.feature_propagation(xyz1, xyz2, p2_rows, p1, chans, relu, self.packed_params(fc))
 
     def forward(self, xyz1, xyz2, points1, points2):
-        _inference_only(self)
         p2_rows = points2.permute(0, 2, 1).contiguous().float()
+        if self.bn_train and self.training:
+            batchnorm.require_batch(xyz1.shape[0] * xyz1.shape[2], (xyz1.shape[0], self.chans[0], xyz1.shape[2]))
+            _lib.require_gpu(xyz1, xyz2, points2)
+            if _wants_grad(self, points2, *(() if points1 is None else (points1,))):
+                return autograd.feature_propagation(self, xyz1, xyz2, points1, p2_rows).permute(0, 2, 1)
+            return batchnorm.fp_train_forward(self, xyz1, xyz2, points1, p2_rows)[0].permute(0, 2, 1)
+        _inference_only(self)
         if _wants_grad(self, points2, *(() if points1 is None else (points1,))):
             return autograd.feature_propagation(self, xyz1, xyz2, points1, p2_rows).permute(0, 2, 1)
         rows = self.run(xyz1, xyz2, points1, p2_rows)
@@ -151,25 +170,38 @@ class PaperFeatExtraction(nn.Module):
     """Paper Sec. 3.1: per-point features (B, N, 32) for every input point.  forward(pts (B, C, N),
     starts=None (3, B) FPS starts, drawn like the reference's sample_and_group when None).  In eval mode
     with autograd on and a parameter (or ``pts``) requiring a gradient the features carry one
-    (``autograd.paper_feat_extraction``: the same kernels and bits); ``.train()`` is refused."""
+    (``autograd.paper_feat_extraction``: the same kernels and bits).  ``bn_train`` (a plain attribute,
+    handed to the three propagations): False, ``.train()`` is refused; True, each set abstraction and each
+    propagation follows its own ``.training`` (batch statistics and a running-statistics update per call
+    in training mode, recorded or not), FPS and the ball queries as ever; two calls (source, then target)
+    each use their own statistics.  The paper's dropout (keep 0.7) stays out, as in the checker."""
 
-    def __init__(self, use_normal=False, **cfg):
+    def __init__(self, use_normal=False, bn_train=False, **cfg):
         super().__init__()
         self.use_normal = use_normal
+        self.bn_train = bool(bn_train)
         sa, fp = paper_fe_config(use_normal, **cfg)
         self.sa1, self.sa2, self.sa3 = (PointNetSetAbstraction(**c) for c in sa)
-        self.fp3, self.fp2, self.fp1 = (PointNetFeaturePropagation(**c) for c in fp)
+        self.fp3, self.fp2, self.fp1 = (PointNetFeaturePropagation(bn_train=self.bn_train, **c) for c in fp)
         self.fc = nn.Linear(32, 32)
 
     def draw_starts(self, B, N):
         return torch.stack([torch.randint(0, n, (B,), dtype=torch.long)
                             for n in (N, self.sa1.npoint, self.sa2.npoint)])
 
+    def _bn_modules(self):
+        return (self.sa1, self.sa2, self.sa3, self.fp3, self.fp2, self.fp1)
+
     def forward(self, pts, starts=None):
-        _inference_only(self)
+        batch_stats = self.bn_train and (self.training or any(m.training for m in self._bn_modules()))
+        if not batch_stats:
+            _inference_only(self)
         B, _, N = pts.shape
         if starts is None:
             starts = self.draw_starts(B, N)
+        if batch_stats:   # the composed path, recorded or not: each module on its own .training
+            _lib.require_gpu(pts)
+            return autograd.paper_feat_extraction(self, pts, starts)
         if _wants_grad(self, pts):
             return autograd.paper_feat_extraction(self, pts, starts)
         xyz = pts[:, :3, :]
@@ -195,10 +227,21 @@ class PaperWeighting(nn.Module):
     linear layers, one HIP launch (dvcp_weighting).  In eval mode with autograd on and a parameter or
     the input requiring a gradient, the scores carry one (backward: dvcp_weighting_backward, the fold
     differentiated by torch down to fc1-3 and bn1-2's weight / bias; running statistics are fixed).
-    Training mode (batch-statistics BN) is refused."""
 
-    def __init__(self):
+    ``bn_train`` (a plain attribute: no parameter or buffer, the state_dict is the same either way).
+    False: training mode is refused.  True: the module follows its own ``.training`` as torch's does.
+    In training mode both BN layers normalise with the mean and biased variance of the call's B N rows
+    and update running_mean / running_var / num_batches_tracked once per forward call (momentum, None
+    included; unbiased variance): ``batchnorm.weighting_train_forward`` on its own entry points
+    (dvcp_weighting_bn_stats / _forward / _backward, no fold), recorded by ``autograd.weighting_bn`` when
+    something requires a gradient, run without recording otherwise (no_grad included: the running
+    statistics are still updated).  A single row (B N = 1) raises ValueError before any launch, as
+    torch does.  In eval mode the paths above, bit for bit.  The paper's dropout (keep 0.7) stays out:
+    the checker has none in either mode."""
+
+    def __init__(self, bn_train=False):
         super().__init__()
+        self.bn_train = bool(bn_train)
         self.fc1, self.bn1 = nn.Linear(32, 16), nn.BatchNorm1d(16)
         self.fc2, self.bn2 = nn.Linear(16, 8), nn.BatchNorm1d(8)
         self.fc3 = nn.Linear(8, 1)
@@ -221,8 +264,15 @@ class PaperWeighting(nn.Module):
 
     def forward(self, f):
         """(B, N, 32) -> (B, N) scores."""
-        _inference_only(self)
         B, N, _ = f.shape
+        if self.bn_train and self.training:
+            batchnorm.require_batch(B * N, f.shape)
+            _lib.require_gpu(f)
+            if _wants_grad(self, f):
+                return autograd.weighting_bn(f.reshape(B * N, 32), self).view(B, N)
+            rows = f.detach().reshape(B * N, 32).contiguous().float()
+            return batchnorm.weighting_train_forward(self, rows)[0].view(B, N)
+        _inference_only(self)
         if _wants_grad(self, f):
             return autograd.weighting(f.reshape(B * N, 32), self).view(B, N)
         return ops.weighting(f.reshape(B * N, 32).contiguous().float(), self.packed_params()).view(B, N)
@@ -252,9 +302,9 @@ class CPG1D(nn.Module):
 
 
 class _Stage(nn.Module):
-    def __init__(self, one_d):
+    def __init__(self, one_d, bn_train=False):
         super().__init__()
-        self.WL = PaperWeighting()
+        self.WL = PaperWeighting(bn_train=bn_train)
         self.DFE = feat_embedding_layer()
         self.cpg = CPG1D() if one_d else _cpg3d()
         self.one_d = one_d
@@ -296,20 +346,37 @@ class DeepVCPPaper(nn.Module):
     target rows go through ``autograd.group_rows`` and ``autograd.dfe_rows`` returns d rows (another
     4 * 32 * 35 * K * C bytes per pair on the target side while backward runs).  A frozen extractor
     under ``train_extractor=True`` is head training, bit for bit.  With the switch off nothing changes,
-    the refusal under ``train_heads=True`` included."""
+    the refusal under ``train_heads=True`` included.
+
+    ``bn_train`` (a plain attribute too, handed to ``FE`` and to both stages' ``PaperWeighting``).  False:
+    ``.train()`` is refused as before.  True: every module follows its own ``.training``, so
+    ``model.train()`` trains with batch statistics throughout and ``model.train(); model.FE.eval()`` is
+    frozen-BN fine-tuning of the extractor under batch-statistics heads.  ``FE`` runs once per cloud (source,
+    then target), each call with its own statistics and its own running update.  A stage whose ``WL`` is
+    in training mode calls it once on all B N source rows (statistics over B N, running statistics
+    updated once per stage and forward; recorded when training, unrecorded otherwise); the top-k runs
+    on the detached scores and ``weights`` is a gather of the recorded scores, so d loss / d weights
+    reaches every row through the BN backward.  It is never called again on the K gathered rows (other
+    statistics, a second update).  With ``WL`` in eval mode the K-row recomputation above is unchanged.
+    ``train_heads`` / ``train_extractor`` keep their meaning: they decide what is recorded, ``.training``
+    which statistics.  DFE, the 3-D CPG and the 1-D CPG have no BatchNorm.  The paper's dropout (keep
+    0.7) stays out: the checker has none in either mode."""
 
     def __init__(self, use_normal=False, K=64, r=2.0, s=0.4, s_z=0.25, d=1.0, nsample=32, duplication=True,
-                 inlier_ratio=0.8, train_heads=False, train_extractor=False, **fe_cfg):
+                 inlier_ratio=0.8, train_heads=False, train_extractor=False, bn_train=False, **fe_cfg):
         super().__init__()
         self.train_heads = bool(train_heads)
         self.train_extractor = bool(train_extractor)
-        self.FE = PaperFeatExtraction(use_normal, **fe_cfg)
-        self.stages = nn.ModuleList([_Stage(False)] + ([_Stage(True)] if duplication else []))
+        self.bn_train = bool(bn_train)
+        self.FE = PaperFeatExtraction(use_normal, bn_train=self.bn_train, **fe_cfg)
+        self.stages = nn.ModuleList([_Stage(one_d, self.bn_train) for one_d in ((False, True) if duplication
+                                                                                 else (False,))])
         self.K, self.r, self.s, self.s_z, self.d, self.ns = K, r, s, s_z, d, nsample
         self.inlier_ratio = inlier_ratio
 
     def forward(self, src, tgt, R_init, t_init, starts=None, keypoint_idx=None):
-        _inference_only(self)
+        if not self.bn_train:
+            _inference_only(self)
         train = (self.train_heads or self.train_extractor) and torch.is_grad_enabled()
         if train:
             if not self.train_extractor and any(p.requires_grad for p in self.FE.parameters()):
@@ -334,10 +401,17 @@ class DeepVCPPaper(nn.Module):
         tc = t_init.to(dev, torch.float64).reshape(-1, 3).expand(B, 3)
         out = []
         for si, st in enumerate(self.stages):
-            with torch.no_grad():
-                score = st.WL(f_src.detach())
+            wl_bn = st.WL.bn_train and st.WL.training
+            if wl_bn:   # batch statistics over all B N rows: one call, recorded when training
+                recorded = st.WL(f_src)
+                score = recorded.detach()
+            else:
+                with torch.no_grad():
+                    score = st.WL(f_src.detach())
             top = ops.topk(score, self.K) if keypoint_idx is None else keypoint_idx[si].to(dev, torch.int64)
-            if train:   # the K selected rows again, recorded: the gathered scores bit for bit
+            if wl_bn:   # never a second call on the K rows: other statistics, a second running update
+                w = torch.gather(recorded, 1, top)
+            elif train:   # the K selected rows again, recorded: the gathered scores bit for bit
                 w = st.WL(torch.gather(f_src, 1, top[..., None].expand(B, self.K, 32)))
             else:
                 w = torch.gather(score, 1, top)

@@ -388,6 +388,9 @@ int dvcp_sa_group_mlp_backward(int dtype, const void* xyz, int64_t sb, int64_t s
  * Replaces the training-mode forward/backward of pointnet2_utils.py:176-202 (BatchNorm2d batch
  * statistics, running-stat update done by the host). */
 int64_t dvcp_sa_bn_pack_floats(int nlayer, const int* chans);
+/* 1 when dvcp_sa_bn_stats / dvcp_sa_bn_zrows / dvcp_sa_bn_backward take the table chans (3 + D, C1, C2[, C3]):
+ * the REF-R tables (sa1 3[+3]-16-16-32, sa2 35-32-64, sa3 67-64-64) and the paper's sa1 (3[+3]-32-32). */
+int dvcp_sa_bn_supported(int nlayer, const int* chans);
 int64_t dvcp_sa_bn_workspace_bytes(int B, int S, int nlayer, const int* chans);
 int64_t dvcp_sa_bn_rows_floats(int B, int S, int nsample, int nlayer, const int* chans);
 int64_t dvcp_sa_bn_feat_workspace_bytes(int B, int S, int nsample, int N, int D);
@@ -547,6 +550,41 @@ int64_t dvcp_weighting_backward_workspace_bytes(int P);
 int dvcp_weighting_backward(const float* feat, int P, const float* params, const float* grad_score,
                             float* grad_feat, void* workspace, int64_t ws_bytes, float* grad_params,
                             void* stream);
+/* The paper's weighting layer under batch-statistics BatchNorm (training mode; csrc/paper_wl_bn.hip).
+ * The three entry points share one arithmetic, y = (W x + b) * scale + shift, a = y > 0 ? y : 0 per BN
+ * layer, on params = W1 (16 x 32) | b1 | scale1 | shift1 | W2 (8 x 16) | b2 | scale2 | shift2 | W3 (8)
+ * | b3: dvcp_weighting_bn_nparams() = 721 floats.  feat: P x 32 fp32.  No BN fold: gamma = 0 is
+ * expressible and the rounding is the same in all three.  No atomics: identical calls, identical bits.
+ *
+ * dvcp_weighting_bn_stats: sums[0..C) = sum over the P rows of layer `layer`'s linear output z (1: fc1,
+ * C = 16; 2: fc2, C = 8), sums[C..2C) = sum z^2, fp64, accumulated in fp64 from the single entries
+ * (per-workgroup partial rows in workspace, folded in index order).  Layer 2 reads layer 1's scale |
+ * shift from params.  The caller turns the sums into mean / biased variance, writes scale = gamma
+ * rstd, shift = beta - mean scale into params, and goes on.  P = 0: sums zeroed.
+ *
+ * dvcp_weighting_bn_forward: score (P fp32) = softplus(fc3(...)) (torch's threshold 20).
+ *
+ * dvcp_weighting_bn_backward: torch's batch-norm backward, dz_l = scale_l (g_a - A_l/M - xhat_l B_l/M),
+ * xhat = (z - mean) rstd, A_l = sum g_a, B_l = sum g_a xhat over the P rows, g_a = g_h [y > 0]; every
+ * pass recomputes the forward exactly and applies softplus' derivative as dvcp_weighting_backward does.
+ * bnstat: mean | rstd | A/M | B/M of bn1 (4 x 16), then of bn2 (4 x 8): 96 fp64 values; xhat and the
+ * mean terms are evaluated in fp64 (with few rows they cancel: at M = 2 to eps / var of their size).
+ * mode 2: sums (2 x 8 fp64) = A_2 | B_2.  mode 1: sums (2 x 16 fp64) = A_1 | B_1, given bn2's A/M, B/M.
+ * mode 0: the gradient pass, given both: grad_feat (optional, P x 32) and grad_params (673 floats: d W1 |
+ * d b1 | d W2 | d b2 | d W3 | d b3, summed over the rows in a fixed order; d gamma_l = B_l and d beta_l
+ * = A_l are the sums of modes 2 and 1).  The output the mode does not write may be NULL.
+ * workspace: ws_bytes >= the entry point's _workspace_bytes(P) (0 for P <= 0).  P = 0: the mode's output
+ * is zeroed and nothing else is touched. */
+int dvcp_weighting_bn_nparams(void);
+int64_t dvcp_weighting_bn_stats_workspace_bytes(int P);
+int dvcp_weighting_bn_stats(const float* feat, int P, const float* params, int layer, void* workspace,
+                            int64_t ws_bytes, double* sums, void* stream);
+int64_t dvcp_weighting_bn_forward_workspace_bytes(int P); /* 0: the forward needs none */
+int dvcp_weighting_bn_forward(const float* feat, int P, const float* params, float* score, void* stream);
+int64_t dvcp_weighting_bn_backward_workspace_bytes(int P);
+int dvcp_weighting_bn_backward(const float* feat, int P, const float* params, const double* bnstat,
+                               const float* grad_score, int mode, float* grad_feat, void* workspace,
+                               int64_t ws_bytes, double* sums, float* grad_params, void* stream);
 /* Backward of dvcp_feature_propagation (training of the paper's extractor).  Nothing is saved by the
  * forward: the 3-NN, the interpolation weights and the layer chain are recomputed per tile of 32
  * rows with the forward's own arithmetic, so the neighbours and the ReLU masks are the forward's.
@@ -571,6 +609,46 @@ int dvcp_feature_propagation_backward(const float* xyz1, int64_t x1b, int64_t x1
                                       const float* bnstat, const float* grad_out, float* grad_p1,
                                       float* grad_p2, void* workspace, int64_t ws_bytes, float* grad_params,
                                       void* stream);
+/* dvcp_feature_propagation under batch-statistics BatchNorm (training mode; csrc/paper_fe_bwd.hip: the
+ * backward kernel's template modes, which recompute the forward's 3-NN, weights and layer chain exactly).
+ * The operands are dvcp_feature_propagation's; params holds, per layer, W | b | scale | shift with the batch
+ * statistics of the layers already known folded into scale | shift (1 | 0 before, and for a fused fc, which
+ * is a plain last layer: no statistics, no mean terms).  Limits are the forward's (4 layers, rows <= 128
+ * wide, layer outputs <= 64, N2 = 2 refused).  Every sum below is accumulated in fp64 from the single
+ * entries, goes through per-(workgroup, row quarter) partial rows in workspace and is folded in index
+ * order: no atomics, identical calls give identical bits.
+ *
+ * dvcp_feature_propagation_bn_stats: sums[0..C) = sum of layer `layer`'s (1-based) conv output z over the
+ * B N1 rows, sums[C..2C) = sum z^2, C = chans[layer].  The caller folds mean / biased variance with gamma,
+ * beta into scale | shift and runs dvcp_feature_propagation itself on the finished params: the train-mode
+ * forward adds no kernel, and the backward's recomputed ReLU masks are the forward's own.
+ *
+ * dvcp_feature_propagation_bn_backward: torch's batch-norm backward, dz_l = scale_l (g_a - A_l/M - xhat_l
+ * B_l/M), xhat = (z - mean) rstd, A_l = sum g_a, B_l = sum g_a xhat, g_a = g_h [a > 0]; xhat and the mean
+ * terms are evaluated in fp64.  bnstat: per layer mean | rstd | A/M | B/M (4 x chans[l + 1] fp64; 0 | 1 | 0 | 0
+ * for a fused fc).  mode = k >= 1: sums (2 x chans[k] fp64) = A_k | B_k, given the layers above k.  mode = 0:
+ * the gradient pass: grad_params (per layer dW | db | dgamma | dbeta as dvcp_feature_propagation_backward;
+ * the caller takes dgamma_l = B_l and dbeta_l = A_l from the sums passes, the packed values are fp32
+ * by-products), grad_p1 (optional, one writer per element) and grad_p2 (optional, through segment_sum;
+ * D2 = 32 or 64).  The output a mode does not write may be NULL.  B = 0 or N1 = 0: the mode's outputs are
+ * zeroed and nothing else is touched. */
+int64_t dvcp_feature_propagation_bn_stats_workspace_bytes(int B, int N1);
+int dvcp_feature_propagation_bn_stats(const float* xyz1, int64_t x1b, int64_t x1c, int64_t x1n, int N1,
+                                      const float* xyz2, int64_t x2b, int64_t x2c, int64_t x2n, int N2, int B,
+                                      const float* p1, int64_t p1b, int64_t p1d, int64_t p1n, int D1,
+                                      const float* p2, int64_t p2b, int64_t p2n, int D2, int nlayer,
+                                      const int* chans, const int* relu, const float* params, int layer,
+                                      void* workspace, int64_t ws_bytes, double* sums, void* stream);
+int64_t dvcp_feature_propagation_bn_backward_workspace_bytes(int B, int N1, int N2, int D2, int nlayer,
+                                                             const int* chans, int want_p2);
+int dvcp_feature_propagation_bn_backward(const float* xyz1, int64_t x1b, int64_t x1c, int64_t x1n, int N1,
+                                         const float* xyz2, int64_t x2b, int64_t x2c, int64_t x2n, int N2, int B,
+                                         const float* p1, int64_t p1b, int64_t p1d, int64_t p1n, int D1,
+                                         const float* p2, int64_t p2b, int64_t p2n, int D2, int nlayer,
+                                         const int* chans, const int* relu, const float* params,
+                                         const double* bnstat, const float* grad_out, int mode, float* grad_p1,
+                                         float* grad_p2, void* workspace, int64_t ws_bytes, double* sums,
+                                         float* grad_params, void* stream);
 /* Backward of dvcp_group_rows in the features: grad_rows B x Q x ns_out x (3 + D) -> grad_feat
  * B x N x D (D = 32 only).  Slot `slot` of centre (b, q) adds its feature columns to point
  * list[(b Q + q) ns_list + (slot < count ? slot : 0)] (padded slots: the first hit); count <= 0 routes

@@ -7,6 +7,11 @@ kind.  One JSON line on stdout.
   python tools/paper_step_bench.py --tag change --events
   python tools/paper_step_bench.py --root <another checkout, built> --kinds heads,infer --tag parent
 
+Kind ``bnheads``: a head-training step after ``model.train(); model.FE.eval()`` on a model built with
+``bn_train=True`` (batch-statistics BN in both weighting layers over a frozen-BN extractor); every
+other kind runs in eval mode.  Kind ``bntrain``: the whole network in training mode (``model.train()``,
+``train_extractor``, every parameter trainable): batch statistics in the extractor and the heads.
+
 --root: the tree whose package is measured (default: this one), for A/B runs in alternating
 processes; a tree without train_extractor takes --kinds heads,infer.  --out: also write the JSON there."""
 import argparse
@@ -37,19 +42,26 @@ kinds = args.kinds.split(",")
 src, tgt, R, t = make_pairs(1, 16384, seed=5)
 src, tgt, R, t = src.float().to(dev), tgt.float().to(dev), R.to(dev), t.to(dev)
 torch.manual_seed(0)
-model = dvcp.paper.DeepVCPPaper(use_normal=False, K=64, r=2.0, s=0.4, s_z=0.25).eval().to(dev)
+flags = {"bn_train": True} if ("bnheads" in kinds or "bntrain" in kinds) else {}   # a tree without the flag is never asked for the kind
+model = dvcp.paper.DeepVCPPaper(use_normal=False, K=64, r=2.0, s=0.4, s_z=0.25, **flags).eval().to(dev)
 starts = torch.stack([model.FE.draw_starts(1, 16384), model.FE.draw_starts(1, 16384)])
 opt = torch.optim.Adam(model.parameters(), lr=1e-5)
 t0 = torch.zeros(1, 3)
 
 
 def step(kind):
+    model.eval()
+    if kind == "bnheads":
+        model.train()
+        model.FE.eval()
+    if kind == "bntrain":
+        model.train()
     if kind == "infer":
         with torch.no_grad():
             return model(src, tgt, R, t0, starts=starts)
-    model.train_heads = kind == "heads"
-    model.train_extractor = kind == "extractor"
-    model.FE.requires_grad_(kind == "extractor")
+    model.train_heads = kind in ("heads", "bnheads")
+    model.train_extractor = kind in ("extractor", "bntrain")
+    model.FE.requires_grad_(kind in ("extractor", "bntrain"))
     opt.zero_grad(set_to_none=True)
     out = model(src, tgt, R, t0, starts=starts)
     loss = 0.0
