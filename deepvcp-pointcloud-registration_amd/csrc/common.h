@@ -164,6 +164,14 @@ __device__ __forceinline__ void linear_sgpr(const float (&x)[CIN], float (&y)[CO
 
 inline int ceil_div(int64_t a, int64_t b) { return static_cast<int>((a + b - 1) / b); }
 
+// fold.hip: out[e] = sum over the nrows partial rows of part[k][e] in fp64, in a fixed order
+// (fold_rows: k ascending; fold_rows_sliced: 16 slices of rows s, s + 16, ..., added in slice order;
+// its rows are ncols apart).  Defined there for the type pairs in use; they only enqueue.
+template <typename PT, typename OT>
+void fold_rows(const PT* part, int nrows, int row_stride, int ncols, OT* out, hipStream_t st);
+template <typename PT, typename OT>
+void fold_rows_sliced(const PT* part, int nrows, int ncols, OT* out, hipStream_t st);
+
 }  // namespace dvcp
 
 #define DVCP_REQUIRE(cond, ...)       \

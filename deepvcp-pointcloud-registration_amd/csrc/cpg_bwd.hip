@@ -18,7 +18,7 @@
 // Convolution weights are read as wave-uniform scalar loads (SGPR operands), so the LDS traffic
 // is one activation read per 16 (conv1 forward) or 32 (conv1 data backward) fmas.
 // Parameter gradients are written per key point (fixed order, no atomics) and summed over key
-// points by cpg_bwd_reduce_kernel in fp64.
+// points by fold_rows (fold.hip) in fp64.
 #include "common.h"
 #include "cpg_grid.h"
 
@@ -506,15 +506,6 @@ __global__ void cpg_bwd_prep_kernel(const float* __restrict__ params, float* __r
 }
 constexpr int kCbWt = 2 * kCbW + 2 * 4 * 16 * 27;
 
-// grad[i] = sum over key points of part[p][i], in fp64, key-point order
-__global__ void cpg_bwd_reduce_kernel(const float* __restrict__ part, int P, float* __restrict__ grad) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= kCbParams) return;
-  double s = 0.0;
-  for (int p = 0; p < P; ++p) s += static_cast<double>(part[static_cast<int64_t>(p) * kCbParams + i]);
-  grad[i] = static_cast<float>(s);
-}
-
 }  // namespace dvcp
 
 extern "C" int64_t dvcp_cpg_backward_workspace_bytes(int P) {
@@ -535,7 +526,7 @@ extern "C" int dvcp_cpg_backward(const float* src, const float* tgt, int64_t t_p
     hipLaunchKernelGGL(dvcp::cpg_bwd_kernel, dim3(P), dim3(dvcp::kCbThreads), 0, st, src, tgt, t_p, t_f, t_c, cand, G,
                        params, grad_vcp, grad_src, grad_tgt, ws, wt);
   }
-  hipLaunchKernelGGL(dvcp::cpg_bwd_reduce_kernel, dim3(dvcp::ceil_div(dvcp::kCbParams, 256)), dim3(256), 0, st, ws,
-                     P > 0 ? P : 0, grad_params);
+  // grad[i] = sum over key points of part[p][i], in fp64, key-point order
+  dvcp::fold_rows(ws, P > 0 ? P : 0, dvcp::kCbParams, dvcp::kCbParams, grad_params, st);
   return dvcp::launch_status("dvcp_cpg_backward");
 }

@@ -21,7 +21,7 @@
 //   9. the blocks' parts summed in block order: parameter partials per key point (outside the
 //      chunk's region, all P of them) and dL/dsrc.
 // and after the last chunk the partials are summed over the key points in fp64, in key-point order
-// (as cpg_bwd_reduce_kernel).  No atomics: every sum has a fixed order, which does not depend on
+// (fold_rows, as the single-tile backward).  No atomics: every sum has a fixed order, which does not depend on
 // how the key points were chunked.
 //
 // A cell outside the grid is 0 in every LDS image: for an activation (cost, h1, h2) that is the
@@ -550,15 +550,6 @@ __global__ void cpg_tb_blocks_kernel(const float* __restrict__ gpb, const float*
     gsrc[static_cast<int64_t>(p) * 32 + i - kTbParams] = s;
 }
 
-// grad[i] = sum over key points of part[p][i], in fp64, key-point order
-__global__ void cpg_tb_reduce_kernel(const float* __restrict__ part, int P, float* __restrict__ grad) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= kTbParams) return;
-  double s = 0.0;
-  for (int p = 0; p < P; ++p) s += static_cast<double>(part[static_cast<int64_t>(p) * kTbParams + i]);
-  grad[i] = static_cast<float>(s);
-}
-
 }  // namespace dvcp
 
 extern "C" int64_t dvcp_cpg_tiled_backward_workspace_bytes(int P, int G) {
@@ -577,8 +568,7 @@ extern "C" int dvcp_cpg_tiled_backward(const float* src, const float* tgt, int64
   DVCP_REQUIRE(params && grad_params, "dvcp_cpg_tiled_backward: null pointer");
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (P <= 0) {
-    hipLaunchKernelGGL(dvcp::cpg_tb_reduce_kernel, dim3(dvcp::ceil_div(dvcp::kTbParams, 256)), dim3(256), 0, s, ws, 0,
-                       grad_params);
+    dvcp::fold_rows(ws, 0, dvcp::kTbParams, dvcp::kTbParams, grad_params, s);
     return dvcp::launch_status("dvcp_cpg_tiled_backward");
   }
   DVCP_REQUIRE(src && tgt && cand && grad_vcp && grad_src && grad_tgt && ws, "dvcp_cpg_tiled_backward: null pointer");
@@ -625,7 +615,6 @@ extern "C" int dvcp_cpg_tiled_backward(const float* src, const float* tgt, int64
     hipLaunchKernelGGL(dvcp::cpg_tb_blocks_kernel, dim3(dvcp::ceil_div(dvcp::kTbPart, 256), np), dim3(256), 0, s, gpb,
                        db3, nblk, part + p0 * dvcp::kTbParams, grad_src + p0 * 32);
   }
-  hipLaunchKernelGGL(dvcp::cpg_tb_reduce_kernel, dim3(dvcp::ceil_div(dvcp::kTbParams, 256)), dim3(256), 0, s, part, P,
-                     grad_params);
+  dvcp::fold_rows(part, P, dvcp::kTbParams, dvcp::kTbParams, grad_params, s);
   return dvcp::launch_status("dvcp_cpg_tiled_backward");
 }

@@ -128,7 +128,7 @@ __device__ __forceinline__ void dfe_tgt_row(PointsView<T> ref, const float* __re
 // dfe_bwd_kernel re-runs the forward rows to find j*, as the forward kernel evaluates them: the
 // collapsed map y = E x + e (dfe_collapse_kernel forms E, e in fp64 and rounds them once to fp32,
 // exactly like dfe_tgt_mfma1_kernel's prologue; 1120 fma per row instead of 3168), and
-// accumulates Gx, gs per workgroup (fixed grid, fixed order: deterministic); dfe_bwd_sum_kernel
+// accumulates Gx, gs per workgroup (fixed grid, fixed order: deterministic); fold_rows_sliced
 // sums the workgroup partials in fp64 and dfe_bwd_finish_kernel applies the map.
 // Workspace: [nblk][32][36] fp32 partials | [32][36] fp64 sums | [32][36] fp32 (E | e).
 constexpr int kDfeGPart = 32 * 36;  // per workgroup: [f][35 Gx + gs]
@@ -157,25 +157,6 @@ __global__ __launch_bounds__(1024) void dfe_collapse_kernel(const float* __restr
     double acc = 0.0;
     for (int a = 0; a < 32; ++a) acc = __fma_rn(static_cast<double>(W3[o * 32 + a]), p[a][c], acc);
     Ee[i] = static_cast<float>(c < 35 ? acc : acc + static_cast<double>(b3[o]));
-  }
-}
-
-// Gs[e] = sum over workgroups of part[k][e] in fp64: 64 elements x 16 slices per workgroup,
-// slices summed in order.
-__global__ __launch_bounds__(1024) void dfe_bwd_sum_kernel(const float* __restrict__ part, int nblk,
-                                                           double* __restrict__ Gs) {
-  __shared__ double sl[16][64];
-  const int tid = threadIdx.x, c = tid & 63, slice = tid >> 6;
-  const int e = blockIdx.x * 64 + c;
-  double s = 0.0;
-  if (e < kDfeGPart)
-    for (int k = slice; k < nblk; k += 16) s += static_cast<double>(part[static_cast<int64_t>(k) * kDfeGPart + e]);
-  sl[slice][c] = s;
-  __syncthreads();
-  if (tid < 64 && e < kDfeGPart) {
-    double t = 0.0;
-    for (int k = 0; k < 16; ++k) t += sl[k][c];
-    Gs[e] = t;
   }
 }
 
@@ -499,8 +480,7 @@ static int dfe_backward_launch(int mode, int dtype, const void* X, const void* r
     dvcp::set_error("dvcp_dfe_backward: bad dtype %d", dtype);
     return DVCP_EINVAL;
   }
-  hipLaunchKernelGGL(dvcp::dfe_bwd_sum_kernel, dim3(dvcp::ceil_div(dvcp::kDfeGPart, 64)), dim3(1024), 0, st, ws, nblk,
-                     Gs);
+  dvcp::fold_rows_sliced(ws, nblk, dvcp::kDfeGPart, Gs, st);
   hipLaunchKernelGGL(dvcp::dfe_bwd_finish_kernel, dim3(1), dim3(1024), 0, st, Gs, params, grad_params);
   if (gF_out) {
     const int rc2 = dvcp::launch_status("dvcp_dfe_tgt_backward");

@@ -1,5 +1,5 @@
-// paper_bwd.hip -- the paper-faithful mode's head backward (DeepVCP paper, Lu et al. ICCV 2019; NOT
-// reference parity, like paper.hip): training of the two stage heads with the extractor frozen.
+// paper_bwd.hip -- the paper-faithful mode's 1-D CPG backward (DeepVCP paper, Lu et al. ICCV 2019; NOT
+// reference parity, like paper.hip).  The weighting layer's backward is in paper_wl_train.hip.
 //
 //   cpg1d_bwd_kernel      backward of cpg1d_kernel (paper Sec. 3.6; csrc/paper.hip): one wave per key
 //                         point recomputes the forward into LDS exactly as the forward does (cost,
@@ -7,29 +7,13 @@
 //                         the softmax / weighted-mean backward and the three transposed convolutions
 //                         there.  d src and d tgt have one writer per element.  The parameter
 //                         gradients stay in registers (each lane owns 24 + 3 + 3 weights) while the
-//                         workgroup walks key points p, p + grid, ...; one partial row per workgroup.
-//   weighting_bwd_kernel  backward of weighting_kernel (paper Sec. 3.2; csrc/head_topk.hip) on the
-//                         folded parameters: a row per lane recomputes the forward with the
-//                         forward's own fma chain (linear_sgpr) and `> 0` test, so the ReLU masks are
-//                         the forward's; softplus' derivative is the logistic of the pre-activation
-//                         (1 on the forward's v > 20 branch).  The rows of a 64-row tile are then
-//                         staged in LDS and every lane adds its 8 + 2 + 1 weights' terms row by row.
-//   fold_partials_kernel  out[e] = sum over the workgroups' partial rows in index order, in fp64.
+//                         workgroup walks key points p, p + grid, ...; one partial row per workgroup,
+//                         folded in index order in fp64 (fold_rows, fold.hip).
 //
 // No atomics anywhere: two identical calls give identical bits.
 #include "common.h"
 
 namespace dvcp {
-
-// out[e] = sum_k part[k][e], k ascending, fp64 accumulator (n <= a few hundred rows).
-__global__ __launch_bounds__(256) void fold_partials_kernel(const float* __restrict__ part, int n, int np,
-                                                            float* __restrict__ out) {
-  const int e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= np) return;
-  double acc = 0.0;
-  for (int k = 0; k < n; ++k) acc += static_cast<double>(part[static_cast<int64_t>(k) * np + e]);
-  out[e] = static_cast<float>(acc);
-}
 
 // ----------------------------------------------------------------------------- 1-D CPG backward
 constexpr int kC1bMaxG = 64;              // cpg1d_kernel's kC1MaxG
@@ -221,130 +205,6 @@ __global__ __launch_bounds__(kC1bMaxG) void cpg1d_bwd_kernel(const float* __rest
   if (z == 0) o3[kC1bW3] = static_cast<float>(db3w);
 }
 
-// ---------------------------------------------------------------------- weighting layer backward
-constexpr int kWlbW1 = 16 * 32, kWlbW2 = 8 * 16;
-constexpr int kWlbParams = kWlbW1 + 16 + kWlbW2 + 8 + 8 + 1;  // PaperWeighting.packed_params()
-constexpr int kWlbRows = 64;                                  // rows per tile: one per lane
-constexpr int kWlbRow = 81;   // x 32 | d h1 16 | h1 16 | d h2 8 | h2 8 | d v 1 (odd: no bank conflicts)
-constexpr int kWlbMaxGrid = 256;
-
-static int wlb_grid(int P) {
-  const int tiles = (P + kWlbRows - 1) / kWlbRows;
-  return tiles < kWlbMaxGrid ? tiles : kWlbMaxGrid;
-}
-
-__global__ __launch_bounds__(kWlbRows) void weighting_bwd_kernel(const float* __restrict__ x, int P,
-                                                                 const float* __restrict__ params,
-                                                                 const float* __restrict__ g, float* __restrict__ gx,
-                                                                 float* __restrict__ partial) {
-  __shared__ float st[kWlbRows][kWlbRow];
-  const int lane = threadIdx.x;
-  const float* w2 = params + kWlbW1 + 16;
-  const float* w3 = w2 + kWlbW2 + 8;
-  // this lane's weights: fc1.W[c1][8 q1 .. + 8], fc2.W[o2][2 q2 .. + 2], fc3.W[0][q2] (lanes < 8)
-  const int c1 = lane >> 2, q1 = lane & 3, o2 = lane >> 3, q2 = lane & 7;
-  float dW1[8], dW2[2] = {0.f, 0.f}, dW3 = 0.f, db1 = 0.f, db2 = 0.f, db3 = 0.f;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) dW1[k] = 0.f;
-  const int tiles = (P + kWlbRows - 1) / kWlbRows;
-  for (int t = blockIdx.x; t < tiles; t += gridDim.x) {
-    const int64_t i = static_cast<int64_t>(t) * kWlbRows + lane;
-    const int nrows = P - t * kWlbRows < kWlbRows ? P - t * kWlbRows : kWlbRows;
-    __syncthreads();  // the previous tile's readers are done
-    if (i < P) {
-      // the forward, as weighting_kernel writes it (same fma chain, same > 0 test)
-      float f[32];
-      const float4* sp = reinterpret_cast<const float4*>(x + i * 32);
-#pragma unroll
-      for (int q = 0; q < 8; ++q) {
-        const float4 v = sp[q];
-        f[4 * q] = v.x;
-        f[4 * q + 1] = v.y;
-        f[4 * q + 2] = v.z;
-        f[4 * q + 3] = v.w;
-      }
-      float p1[16], p2[8], p3[1];
-      linear_sgpr<32, 16>(f, p1, params);
-      float a1[16], a2[8];
-#pragma unroll
-      for (int c = 0; c < 16; ++c) a1[c] = p1[c] > 0.0f ? p1[c] : 0.0f;
-      linear_sgpr<16, 8>(a1, p2, w2);
-#pragma unroll
-      for (int c = 0; c < 8; ++c) a2[c] = p2[c] > 0.0f ? p2[c] : 0.0f;
-      linear_sgpr<8, 1>(a2, p3, w3);
-      const float v = p3[0];
-      // softplus'(v) = 1 / (1 + exp(-v)); the forward's v > 20 branch is the identity
-      const float gvv = g[i] * (v > 20.0f ? 1.0f : 1.0f / (1.0f + expf(-v)));
-      float g2[8], g1[16];
-#pragma unroll
-      for (int c = 0; c < 8; ++c) g2[c] = p2[c] > 0.0f ? w3[c] * gvv : 0.0f;
-#pragma unroll
-      for (int c = 0; c < 16; ++c) {
-        float acc = 0.f;
-#pragma unroll
-        for (int o = 0; o < 8; ++o) acc = __fmaf_rn(w2[o * 16 + c], g2[o], acc);
-        g1[c] = p1[c] > 0.0f ? acc : 0.0f;
-      }
-      if (gx) {
-        float4* dp = reinterpret_cast<float4*>(gx + i * 32);
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-          float r[4];
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            float acc = 0.f;
-#pragma unroll
-            for (int c = 0; c < 16; ++c) acc = __fmaf_rn(params[c * 32 + 4 * q + j], g1[c], acc);
-            r[j] = acc;
-          }
-          dp[q] = make_float4(r[0], r[1], r[2], r[3]);
-        }
-      }
-      float* s = st[lane];
-#pragma unroll
-      for (int k = 0; k < 32; ++k) s[k] = f[k];
-#pragma unroll
-      for (int k = 0; k < 16; ++k) {
-        s[32 + k] = g1[k];
-        s[48 + k] = a1[k];
-      }
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        s[64 + k] = g2[k];
-        s[72 + k] = a2[k];
-      }
-      s[80] = gvv;
-    }
-    __syncthreads();
-    // the tile's rows in order: dW = sum_rows (d out) (in)^T, db = sum_rows d out
-    for (int r = 0; r < nrows; ++r) {
-      const float* s = st[r];
-      const float a = s[32 + c1];
-      db1 += a;
-#pragma unroll
-      for (int k = 0; k < 8; ++k) dW1[k] = __fmaf_rn(a, s[8 * q1 + k], dW1[k]);
-      const float b = s[64 + o2];
-      db2 += b;
-#pragma unroll
-      for (int k = 0; k < 2; ++k) dW2[k] = __fmaf_rn(b, s[48 + 2 * q2 + k], dW2[k]);
-      const float c = s[80];
-      db3 += c;
-      dW3 = __fmaf_rn(c, s[72 + q2], dW3);
-    }
-  }
-  float* o = partial + static_cast<int64_t>(blockIdx.x) * kWlbParams;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) o[c1 * 32 + 8 * q1 + k] = dW1[k];
-  if (q1 == 0) o[kWlbW1 + c1] = db1;
-  float* p2o = o + kWlbW1 + 16;
-#pragma unroll
-  for (int k = 0; k < 2; ++k) p2o[o2 * 16 + 2 * q2 + k] = dW2[k];
-  if (q2 == 0) p2o[kWlbW2 + o2] = db2;
-  float* p3o = p2o + kWlbW2 + 8;
-  if (lane < 8) p3o[lane] = dW3;
-  if (lane == 0) p3o[8] = db3;
-}
-
 }  // namespace dvcp
 
 extern "C" int64_t dvcp_cpg1d_backward_workspace_bytes(int P) {
@@ -373,37 +233,6 @@ extern "C" int dvcp_cpg1d_backward(const float* src, const float* tgt, const flo
   hipLaunchKernelGGL(dvcp::cpg1d_bwd_kernel, dim3(grid), dim3(dvcp::kC1bMaxG), 0, st, src, tgt, cand, P, Gz, params,
                      grad_vcp, grad_src, grad_tgt, ws);
   if (int e = dvcp::launch_status("dvcp_cpg1d_backward")) return e;
-  hipLaunchKernelGGL(dvcp::fold_partials_kernel, dim3(dvcp::ceil_div(dvcp::kC1bParams, 256)), dim3(256), 0, st, ws,
-                     grid, dvcp::kC1bParams, grad_params);
+  dvcp::fold_rows(ws, grid, dvcp::kC1bParams, dvcp::kC1bParams, grad_params, st);
   return dvcp::launch_status("dvcp_cpg1d_backward(sum)");
-}
-
-extern "C" int64_t dvcp_weighting_backward_workspace_bytes(int P) {
-  if (P <= 0) return 0;
-  return static_cast<int64_t>(dvcp::wlb_grid(P)) * dvcp::kWlbParams * 4;
-}
-
-extern "C" int dvcp_weighting_backward(const float* feat, int P, const float* params, const float* grad_score,
-                                       float* grad_feat, void* workspace, int64_t ws_bytes, float* grad_params,
-                                       void* stream) {
-  DVCP_REQUIRE(P >= 0, "dvcp_weighting_backward: P=%d is negative", P);
-  DVCP_REQUIRE(params && grad_params, "dvcp_weighting_backward: null pointer");
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  if (P == 0) {
-    if (hipMemsetAsync(grad_params, 0, dvcp::kWlbParams * 4, st) != hipSuccess)
-      return dvcp::launch_status("dvcp_weighting_backward(empty)");
-    return DVCP_OK;
-  }
-  DVCP_REQUIRE(feat && grad_score && workspace, "dvcp_weighting_backward: null pointer");
-  const int64_t need = dvcp_weighting_backward_workspace_bytes(P);
-  DVCP_REQUIRE(ws_bytes >= need, "dvcp_weighting_backward: workspace of %lld bytes is short of %lld",
-               static_cast<long long>(ws_bytes), static_cast<long long>(need));
-  const int grid = dvcp::wlb_grid(P);
-  float* ws = static_cast<float*>(workspace);
-  hipLaunchKernelGGL(dvcp::weighting_bwd_kernel, dim3(grid), dim3(dvcp::kWlbRows), 0, st, feat, P, params, grad_score,
-                     grad_feat, ws);
-  if (int e = dvcp::launch_status("dvcp_weighting_backward")) return e;
-  hipLaunchKernelGGL(dvcp::fold_partials_kernel, dim3(dvcp::ceil_div(dvcp::kWlbParams, 256)), dim3(256), 0, st, ws,
-                     grid, dvcp::kWlbParams, grad_params);
-  return dvcp::launch_status("dvcp_weighting_backward(sum)");
 }

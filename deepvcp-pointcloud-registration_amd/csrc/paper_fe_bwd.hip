@@ -15,7 +15,7 @@
 //                         Coordinates carry no gradient, so the interpolation weights are constants.
 //                         Parameter gradients stay in registers (thread (o, kq) owns dW[o][kq + 4 j])
 //                         while min(tiles, 256) workgroups walk tiles t, t + grid, ...; one partial row
-//                         per workgroup, folded in index order in fp64 by fe_fold_partials_kernel.
+//                         per workgroup, folded in index order in fp64 by fold_rows (fold.hip).
 //                         grad_p1 has one writer per element.  grad_p2 is a scatter over the three
 //                         neighbours: entry e = (b N1 + n) 3 + i gets the key b N2 + idx_i (the
 //                         sentinel for i >= min(N2, 3)) and the row w_i g_x[D1..], and segment_sum
@@ -61,16 +61,6 @@ int fb_nparams(int nlayer, const int* chans) {
   int P = 0;
   for (int l = 0; l < nlayer; ++l) P += chans[l] * chans[l + 1] + 3 * chans[l + 1];
   return P;
-}
-
-// out[e] = sum_k part[k][e], k ascending, fp64 accumulator (paper_bwd.hip's fold).
-__global__ __launch_bounds__(256) void fe_fold_partials_kernel(const float* __restrict__ part, int n, int np,
-                                                               float* __restrict__ out) {
-  const int e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= np) return;
-  double acc = 0.0;
-  for (int k = 0; k < n; ++k) acc += static_cast<double>(part[static_cast<int64_t>(k) * np + e]);
-  out[e] = static_cast<float>(acc);
 }
 
 // One layer's parameter-gradient terms of a tile, rows in order.  Thread (o, kq) owns dW[o][kq + 4 j].
@@ -511,8 +501,7 @@ extern "C" int dvcp_feature_propagation_backward(
                      B, p1, p1b, p1d, p1n, D1, p2, p2b, p2n, D2, lay, params, bnstat, grad_out, grad_p1, keys, contrib,
                      np, partial, nullptr, 0, nullptr);
   if (int e = dvcp::launch_status("dvcp_feature_propagation_backward")) return e;
-  hipLaunchKernelGGL(dvcp::fe_fold_partials_kernel, dim3(dvcp::ceil_div(np, 256)), dim3(256), 0, st, partial, grid, np,
-                     grad_params);
+  dvcp::fold_rows(partial, grid, np, np, grad_params, st);
   if (int e = dvcp::launch_status("dvcp_feature_propagation_backward(sum)")) return e;
   if (grad_p2) return dvcp::segment_sum(keys, contrib, E, static_cast<int64_t>(B) * N2, D2, grad_p2, w, st);
   return DVCP_OK;
@@ -652,8 +641,7 @@ extern "C" int dvcp_feature_propagation_bn_backward(
                      p1, p1b, p1d, p1n, D1, p2, p2b, p2n, D2, lay, params, nullptr, grad_out, grad_p1, keys, contrib,
                      np, partial, bnstat, 0, nullptr);
   if (int e = dvcp::launch_status(who)) return e;
-  hipLaunchKernelGGL(dvcp::fe_fold_partials_kernel, dim3(dvcp::ceil_div(np, 256)), dim3(256), 0, st, partial, grid, np,
-                     grad_params);
+  dvcp::fold_rows(partial, grid, np, np, grad_params, st);
   if (int e = dvcp::launch_status("dvcp_feature_propagation_bn_backward(fold)")) return e;
   if (grad_p2) return dvcp::segment_sum(keys, contrib, E, static_cast<int64_t>(B) * N2, D2, grad_p2, w, st);
   return DVCP_OK;

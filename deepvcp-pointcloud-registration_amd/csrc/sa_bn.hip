@@ -664,24 +664,6 @@ __global__ __launch_bounds__(kBnThreads) __attribute__((amdgpu_waves_per_eu(2)))
   }
 }
 
-// out[e] = sum over the nw partial rows of part[k][e] in fp64, in a fixed order (deterministic).
-template <typename PT, typename OT>
-__global__ __launch_bounds__(1024) void bn_sum_kernel(const PT* __restrict__ part, int nw, int P, OT* __restrict__ out) {
-  __shared__ double sl[16][64];
-  const int tid = threadIdx.x, c = tid & 63, slice = tid >> 6;
-  const int e = blockIdx.x * 64 + c;
-  double acc = 0.0;
-  if (e < P)
-    for (int k = slice; k < nw; k += 16) acc += static_cast<double>(part[static_cast<int64_t>(k) * P + e]);
-  sl[slice][c] = acc;
-  __syncthreads();
-  if (tid < 64 && e < P) {
-    double t = 0.0;
-    for (int k = 0; k < 16; ++k) t += sl[k][c];
-    out[e] = static_cast<OT>(t);
-  }
-}
-
 // segsum.hip
 int64_t segment_sum_workspace_bytes(int64_t E, int64_t nrows);
 int segment_sum(const uint32_t* keys, const float* contrib, int64_t E, int64_t nrows, int ncol, float* out, void* ws,
@@ -729,8 +711,7 @@ static int launch_stats(const BnArgs& a, void* ws, double* sums, float* zrows) {
   hipLaunchKernelGGL((sa_bn_stats_kernel<T, FT, D, C1, C2, C3, LAYER>), dim3(grid), dim3(kBnThreads), 0, a.st, pv,
                      cv, a.S, a.B, fv, a.count, a.list, a.nsample, a.pack, part, zrows);
   if (int e = launch_status("dvcp_sa_bn_stats")) return e;
-  hipLaunchKernelGGL((bn_sum_kernel<double, double>), dim3(ceil_div(2 * CZ, 64)), dim3(1024), 0, a.st, part,
-                     grid * kBnWaves, 2 * CZ, sums);
+  fold_rows_sliced(part, grid * kBnWaves, 2 * CZ, sums, a.st);
   return launch_status("dvcp_sa_bn_stats(sum)");
 }
 
@@ -766,8 +747,7 @@ static int launch_bwd(const BnArgs& a, const float* zrows, const float* gout, fl
   }
   if constexpr (MODE != 0) {
     constexpr int CM = MODE == 1 ? C1 : (MODE == 2 ? C2 : C3);
-    hipLaunchKernelGGL((bn_sum_kernel<double, double>), dim3(ceil_div(2 * CM, 64)), dim3(1024), 0, a.st,
-                       static_cast<const double*>(ws), grid * kBnWaves, 2 * CM, sums);
+    fold_rows_sliced(static_cast<const double*>(ws), grid * kBnWaves, 2 * CM, sums, a.st);
     return launch_status("dvcp_sa_bn_backward(sum)");
   }
   return DVCP_OK;

@@ -1057,26 +1057,8 @@ __global__ __launch_bounds__(256) void bnm_pre_kernel(const float* __restrict__ 
   reinterpret_cast<float4*>(U + i * C1)[g] = acc;
 }
 
-// out[e] = sum over the nw partial rows of part[k][e] in fp64, in a fixed order.
-template <typename PT, typename OT>
-__global__ __launch_bounds__(1024) void bnm_sum_kernel(const PT* __restrict__ part, int nw, int P, OT* __restrict__ out) {
-  __shared__ double sl[16][64];
-  const int tid = threadIdx.x, c = tid & 63, slice = tid >> 6;
-  const int e = blockIdx.x * 64 + c;
-  double acc = 0.0;
-  if (e < P)
-    for (int k = slice; k < nw; k += 16) acc += static_cast<double>(part[static_cast<int64_t>(k) * P + e]);
-  sl[slice][c] = acc;
-  __syncthreads();
-  if (tid < 64 && e < P) {
-    double t = 0.0;
-    for (int k = 0; k < 16; ++k) t += sl[k][c];
-    out[e] = static_cast<OT>(t);
-  }
-}
-
 // Slice sums of the partial rows: block (column group, slice s) sums rows [s per, (s + 1) per) in
-// a fixed order into tmp[s] (fp64); bnm_sum_kernel then adds the slices in order.  (One workgroup
+// a fixed order into tmp[s] (fp64); fold_rows_sliced then adds the slices in order.  (One workgroup
 // per 64 columns over thousands of rows was latency-bound: 0.13 ms for a 128-column statistic.)
 template <typename PT>
 __global__ __launch_bounds__(1024) void bnm_slice_kernel(const PT* __restrict__ part, int nrows, int P, int per,
@@ -1261,7 +1243,7 @@ int bnm_reduce(const PT* part, int nrows, int P, OT* out, void* ws, int64_t tmp_
   const int per = (nrows + kSumSlices - 1) / kSumSlices;
   const int ns = (nrows + per - 1) / per;
   hipLaunchKernelGGL((bnm_slice_kernel<PT>), dim3(ceil_div(P, 64), ns), dim3(1024), 0, st, part, nrows, P, per, tmp);
-  hipLaunchKernelGGL((bnm_sum_kernel<double, OT>), dim3(ceil_div(P, 64)), dim3(1024), 0, st, tmp, ns, P, out);
+  fold_rows_sliced(tmp, ns, P, out, st);
   return launch_status("dvcp_sa_bnm_pass(sum)");
 }
 int bnm_sums(void* ws, int nw, int C, double* sums, int64_t tmp_off, hipStream_t st) {

@@ -392,6 +392,23 @@ def _wanted(ctx, first, grads, dtypes):
             for k, (g, dt) in enumerate(zip(grads, dtypes))]
 
 
+def _fp_grads(ctx, gp, gp1, gp2, chans, nconv):
+    """The tail of both propagation backwards: the packed gradient and the (B, N1, D1) / (B, N2, D2) rows
+    as backward's return tuple."""
+    per = _layer_grads(gp, chans, [ctx.shapes[4 * l][0] for l in range(nconv)] + [ctx.shapes[-2][0]])
+    grads = per[:4 * nconv + (2 if len(chans) - 1 > nconv else 0)]   # a fused fc: its dgamma / dbeta are discarded
+    gp1 = gp1.permute(0, 2, 1).to(ctx.in_dtypes[0]) if gp1 is not None else None
+    gp2 = gp2.to(ctx.in_dtypes[1]) if gp2 is not None else None
+    return (None, None, None, None, gp1, gp2, *_wanted(ctx, 6, grads, [dt for _, dt in ctx.shapes]))
+
+
+def _sa_grads(ctx, gp, gF, chans):
+    """The tail of both set-abstraction backwards, likewise."""
+    grads = _layer_grads(gp, chans, [ctx.shapes[4 * l][0] for l in range(len(chans) - 1)])
+    gF = gF.permute(0, 2, 1).to(ctx.feat_dtype) if gF is not None else None
+    return (None, None, None, gF, None, None, None, *_wanted(ctx, 7, grads, [dt for _, dt in ctx.shapes]))
+
+
 class _FeatureProp(torch.autograd.Function):
     """forward(fp, fc, xyz1, xyz2, p1, p2_rows, *[conv.weight, conv.bias, bn.weight, bn.bias per layer,
     then fc.weight, fc.bias]): saves the operands only; the backward recomputes the rest."""
@@ -421,14 +438,7 @@ class _FeatureProp(torch.autograd.Function):
         want_p2 = ctx.needs_input_grad[5]
         gp, gp1, gp2 = ops.feature_propagation_backward(xyz1, xyz2, p2, p1, ctx.chans, ctx.relu, packed, bnstat, g,
                                                         want_p1=want_p1, want_p2=want_p2)
-        wshapes = [ctx.shapes[4 * l][0] for l in range(ctx.nconv)] + [ctx.shapes[-2][0]]
-        per = _layer_grads(gp, ctx.chans, wshapes)
-        grads = per[:4 * ctx.nconv]
-        if len(ctx.chans) - 1 > ctx.nconv:      # the fused fc: its dgamma / dbeta are discarded
-            grads += per[4 * ctx.nconv:4 * ctx.nconv + 2]
-        gp1 = gp1.permute(0, 2, 1).to(ctx.in_dtypes[0]) if want_p1 else None
-        gp2 = gp2.to(ctx.in_dtypes[1]) if want_p2 else None
-        return (None, None, None, None, gp1, gp2, *_wanted(ctx, 6, grads, [dt for _, dt in ctx.shapes]))
+        return _fp_grads(ctx, gp, gp1, gp2, ctx.chans, ctx.nconv)
 
 
 class _FeaturePropBN(torch.autograd.Function):
@@ -452,15 +462,7 @@ class _FeaturePropBN(torch.autograd.Function):
         want_p1 = p1 is not None and ctx.needs_input_grad[4]
         want_p2 = ctx.needs_input_grad[5]
         gp, gp1, gp2 = batchnorm.fp_train_backward(st, xyz1, xyz2, p1, p2, g, want_p1=want_p1, want_p2=want_p2)
-        nconv, chans = st["nbn"], st["chans"]
-        wshapes = [ctx.shapes[4 * l][0] for l in range(nconv)] + [ctx.shapes[-2][0]]
-        per = _layer_grads(gp, chans, wshapes)
-        grads = per[:4 * nconv]
-        if len(chans) - 1 > nconv:      # the fused fc: its dgamma / dbeta are discarded
-            grads += per[4 * nconv:4 * nconv + 2]
-        gp1 = gp1.permute(0, 2, 1).to(ctx.in_dtypes[0]) if want_p1 else None
-        gp2 = gp2.to(ctx.in_dtypes[1]) if want_p2 else None
-        return (None, None, None, None, gp1, gp2, *_wanted(ctx, 6, grads, [dt for _, dt in ctx.shapes]))
+        return _fp_grads(ctx, gp, gp1, gp2, st["chans"], st["nbn"])
 
 
 def _fp_tensors(fp, fc=None):
@@ -522,9 +524,7 @@ class _SaGroupMlp(torch.autograd.Function):
         want_feat = feat is not None and ctx.needs_input_grad[3]
         gp, gF = ops.sa_group_mlp_backward(xyz, ctr, feat, count, lst, ctx.ns, ctx.chans, packed, bnstat, g,
                                            want_feat_grad=want_feat)
-        grads = _layer_grads(gp, ctx.chans, [ctx.shapes[4 * l][0] for l in range(len(ctx.chans) - 1)])
-        gF = gF.permute(0, 2, 1).to(ctx.feat_dtype) if want_feat else None
-        return (None, None, None, gF, None, None, None, *_wanted(ctx, 7, grads, [dt for _, dt in ctx.shapes]))
+        return _sa_grads(ctx, gp, gF, ctx.chans)
 
 
 class _SaGroupMlpBN(torch.autograd.Function):
@@ -545,9 +545,7 @@ class _SaGroupMlpBN(torch.autograd.Function):
         want_feat = ctx.lay["feat"] is not None and ctx.needs_input_grad[3]
         gp, gF = batchnorm.train_backward(ctx.sa, ctx.lay, g, want_feat_grad=want_feat)
         ctx.lay = None
-        grads = _layer_grads(gp, ctx.sa.chans, [ctx.shapes[4 * l][0] for l in range(len(ctx.sa.chans) - 1)])
-        gF = gF.permute(0, 2, 1).to(ctx.feat_dtype) if want_feat else None
-        return (None, None, None, gF, None, None, None, *_wanted(ctx, 7, grads, [dt for _, dt in ctx.shapes]))
+        return _sa_grads(ctx, gp, gF, ctx.sa.chans)
 
 
 def paper_feat_extraction(fe, pts, starts):

@@ -28,7 +28,7 @@ over the rows' 65536-entry chunks, chunk sums in fp64).
 Paper mode (dvcp/paper.py, ``bn_train=True``): the paper's sa1 table (3[+3]-32-32) takes the
 lane-per-entry passes above; the feature propagations and the weighting layer have their own pairs at
 the end of this file (``fp_train_forward`` / ``fp_train_backward``, csrc/paper_fe_bwd.hip's template
-modes; ``weighting_train_forward`` / ``weighting_train_backward``, csrc/paper_wl_bn.hip).
+modes; ``weighting_train_forward`` / ``weighting_train_backward``, csrc/paper_wl_train.hip).
 """
 import torch
 
@@ -73,17 +73,39 @@ def _bnm_pack(sa, dev):
     return pack, offs
 
 
-def _set_stats(pack, bn, o, cin, cout, sums, M):
-    """Batch mean / variance of one layer from its sums; scale, shift, mean, istd into the pack and
-    the running-statistics update."""
+def _batch_stats(bn, sums, M):
+    """One BN layer's batch statistics from its fp64 sums (sum z | sum z^2 over the M values per
+    channel): (mean, biased variance, rstd, scale, shift) in fp64, gamma and beta folded into scale |
+    shift; and the running-statistics update."""
     mean = sums[0] / M
     var = (sums[1] / M - mean * mean).clamp_min(0.0)
-    istd = torch.rsqrt(var + bn.eps)
-    scale = bn.weight.double() * istd
+    rstd = torch.rsqrt(var + bn.eps)
+    scale = bn.weight.double() * rstd
     shift = bn.bias.double() - mean * scale
+    _update_running(bn, mean, var, M)
+    return mean, var, rstd, scale, shift
+
+
+def _backward_sums(layers, sums_pass, out, M):
+    """The backward's sums A = sum g_a | B = sum g_a xhat of every BN layer, the top layer first:
+    ``layers`` lists (mode, offset, channels) top-down, ``sums_pass(mode)`` runs one layer's pass ->
+    (2, C) fp64, which needs A/M | B/M of the layers above: written to ``out[offset:offset + 2 C]``
+    before the next pass.  M = 0: zero sums, nothing written.  Returns {mode: sums}."""
+    sums = {}
+    for mode, off, c in layers:
+        if M:
+            sums[mode] = sums_pass(mode)
+            out[off:off + 2 * c] = (sums[mode] / M).reshape(-1)
+        else:
+            sums[mode] = torch.zeros(2, c, dtype=torch.float64, device=out.device)
+    return sums
+
+
+def _set_stats(pack, bn, o, cin, cout, sums, M):
+    """scale, shift, mean, istd of one layer into the dvcp_sa_bn pack."""
+    mean, _, istd, scale, shift = _batch_stats(bn, sums, M)
     v = o + cout * cin + cout
     pack[v:v + 4 * cout] = torch.cat([scale, shift, mean, istd]).float()
-    _update_running(bn, mean, var, M)
 
 
 def _train_forward_mfma(sa, xyz, ctr, feat, count, lst, ns):
@@ -182,17 +204,13 @@ def train_backward(sa, lay, g_out, want_feat_grad):
     zrows = st.pop("zrows", None)
     if zrows is None:
         zrows = ops.sa_bn_zrows(*args, st["pack"])
-    sums = [None] * len(offs)
-    for k in range(len(offs), 0, -1):   # the top layer's sums first: each lower one needs those above
-        s = ops.sa_bn_backward(*args, pack, zrows, g, k)
-        o, cin, cout = offs[k - 1]
-        v = o + cout * cin + 5 * cout
-        pack[v:v + 2 * cout] = (s / M).reshape(-1).float()
-        sums[k - 1] = s
+    layers = [(k, o + cout * cin + 5 * cout, cout) for k, (o, cin, cout) in reversed(list(enumerate(offs, 1)))]
+    sums = _backward_sums(layers, lambda k: ops.sa_bn_backward(*args, pack, zrows, g, k), pack, M)
     rows, gF = ops.sa_bn_backward(*args, pack, zrows, g, 0, want_feat_grad=want_feat_grad)
     del zrows
     parts = []
-    for (o, cin, cout), s, (gz, ha) in zip(offs, sums, rows):
+    for k, ((o, cin, cout), (gz, ha)) in enumerate(zip(offs, rows), 1):
+        s = sums[k]
         dwb = _gemm_nt(gz, ha)                  # [dW | db] = dz [h; 1]^T over the M entries
         parts += [dwb[:, :cin].reshape(-1), dwb[:, cin], s[1], s[0]]   # dW, db, dgamma, dbeta
     return torch.cat([p.float() for p in parts]), gF
@@ -236,15 +254,10 @@ def fp_train_forward(fp, xyz1, xyz2, p1, p2_rows, fc=None):
             elif M:
                 bn = fp.mlp_bns[layer - 1]
                 sums = ops.feature_propagation_bn_stats(xyz1, xyz2, p2_rows, p1, chans, relu, pack, layer)
-                mean = sums[0] / M
-                var = (sums[1] / M - mean * mean).clamp_min(0.0)
-                rstd = torch.rsqrt(var + bn.eps)
-                scale = bn.weight.double() * rstd
-                shift = bn.bias.double() - mean * scale
+                mean, _, rstd, scale, shift = _batch_stats(bn, sums, M)
                 v = o + co * ci + co
                 pack[v:v + 2 * co] = torch.cat([scale, shift]).float()
                 bnstat[so:so + 2 * co] = torch.cat([mean, rstd])
-                _update_running(bn, mean, var, M)
             so += 4 * co
         if M:
             out = ops.feature_propagation(xyz1, xyz2, p2_rows, p1, chans, relu, pack)
@@ -261,13 +274,8 @@ def fp_train_backward(st, xyz1, xyz2, p1, p2_rows, g, want_p1=True, want_p2=True
     chans, relu, M = st["chans"], st["relu"], st["M"]
     bnstat = st["bnstat"].clone()
     args = (xyz1, xyz2, p2_rows, p1, chans, relu, st["pack"])
-    so = [4 * sum(chans[1:l]) for l in range(1, len(chans))]
-    sums = {}
-    for k in range(st["nbn"], 0, -1):
-        co = chans[k]
-        sums[k] = ops.feature_propagation_bn_backward(*args, bnstat, g, k)
-        if M:
-            bnstat[so[k - 1] + 2 * co:so[k - 1] + 4 * co] = (sums[k] / M).reshape(-1)
+    layers = [(k, 4 * sum(chans[1:k]) + 2 * chans[k], chans[k]) for k in range(st["nbn"], 0, -1)]
+    sums = _backward_sums(layers, lambda k: ops.feature_propagation_bn_backward(*args, bnstat, g, k), bnstat, M)
     gp, gp1, gp2 = ops.feature_propagation_bn_backward(*args, bnstat, g, 0, want_p1=want_p1, want_p2=want_p2)
     o = 0
     for k, (ci, co) in enumerate(zip(chans[:-1], chans[1:]), 1):
@@ -277,7 +285,7 @@ def fp_train_backward(st, xyz1, xyz2, p1, p2_rows, g, want_p1=True, want_p2=True
     return gp, gp1, gp2
 
 
-# ---- paper mode: the weighting layer (dvcp.paper.PaperWeighting, csrc/paper_wl_bn.hip) -------------
+# ---- paper mode: the weighting layer (dvcp.paper.PaperWeighting, csrc/paper_wl_train.hip) -------------
 # (offset, C_in, C_out) of fc1 / fc2 in the train-mode pack W | b | scale | shift, then fc3, and the
 # offset of each BN layer's mean | rstd | A/M | B/M in the statistics vector
 _WL_LAYERS = ((0, 32, 16), (32 * 16 + 3 * 16, 16, 8))
@@ -311,16 +319,10 @@ def weighting_train_forward(wl, rows):
         if P == 0:
             return torch.empty(0, dtype=torch.float32, device=dev), dict(pack=pack, bnstat=bnstat, M=0, rows=rows)
         for layer, (bn, (o, cin, cout), so) in enumerate(zip((wl.bn1, wl.bn2), _WL_LAYERS, _WL_STAT), 1):
-            sums = ops.weighting_bn_stats(rows, pack, layer)
-            mean = sums[0] / P
-            var = (sums[1] / P - mean * mean).clamp_min(0.0)
-            rstd = torch.rsqrt(var + bn.eps)
-            scale = bn.weight.double() * rstd
-            shift = bn.bias.double() - mean * scale
+            mean, _, rstd, scale, shift = _batch_stats(bn, ops.weighting_bn_stats(rows, pack, layer), P)
             v = o + cout * cin + cout
             pack[v:v + 2 * cout] = torch.cat([scale, shift]).float()
             bnstat[so:so + 2 * cout] = torch.cat([mean, rstd])
-            _update_running(bn, mean, var, P)
         score = ops.weighting_bn_forward(rows, pack)
     return score, dict(pack=pack, bnstat=bnstat, M=P, rows=rows)
 
@@ -332,14 +334,8 @@ def weighting_train_backward(wl, st, g, want_feat):
     (mode 1), then the gradient pass (mode 0); d gamma = B and d beta = A are the sums themselves."""
     pack, M, rows = st["pack"], st["M"], st["rows"]
     bnstat = st["bnstat"].clone()
-    sums = {}
-    if M:
-        for mode, so, c in ((2, _WL_STAT[1], 8), (1, _WL_STAT[0], 16)):
-            sums[mode] = ops.weighting_bn_backward(rows, pack, bnstat, g, mode)
-            bnstat[so + 2 * c:so + 4 * c] = (sums[mode] / M).reshape(-1)
-    else:
-        sums = {2: torch.zeros(2, 8, dtype=torch.float64, device=rows.device),
-                1: torch.zeros(2, 16, dtype=torch.float64, device=rows.device)}
+    layers = ((2, _WL_STAT[1] + 2 * 8, 8), (1, _WL_STAT[0] + 2 * 16, 16))
+    sums = _backward_sums(layers, lambda mode: ops.weighting_bn_backward(rows, pack, bnstat, g, mode), bnstat, M)
     gp, gfeat = ops.weighting_bn_backward(rows, pack, bnstat, g, 0, want_feat=want_feat)
     w1, b1, w2, b2, w3, b3 = torch.split(gp, [16 * 32, 16, 8 * 16, 8, 8, 1])
     grads = [w1.view(16, 32), b1, sums[1][1].float(), sums[1][0].float(),

@@ -20,6 +20,38 @@ def _pts(t, pdim):
     return t.shape[pdim], sb, sc, sn
 
 
+def _workspace(query, *args, device):
+    """A fp32 workspace of the size the entry point ``query`` answers for ``args`` (bytes)."""
+    nbytes = int(getattr(_lib.load(), query)(*args))
+    if nbytes < 0:
+        raise RuntimeError(f"{query}: size query failed")
+    return torch.empty(max(1, (nbytes + 3) // 4), dtype=torch.float32, device=device)
+
+
+def _sa_operands(xyz, ctr, feat, count, lst, nsample, chans, xyz_pdim=2, feat_ddim=1, feat_pdim=2, ctr_pdim=2,
+                 dtypes=True):
+    """The grouping operands the set-abstraction entry points share: (the argument tuple -- points, centres,
+    feature view (``feat`` None or (B, D, N)-indexable), lists, layer count and channels --, (B, N, S, D), the
+    host ``chans`` array, which the caller keeps alive over its calls).  ``dtypes=False``: without the two
+    dtype codes (the matrix-core passes take fp32 only)."""
+    B = xyz.shape[0]
+    N, sb, sc, sn = _pts(xyz, xyz_pdim)
+    S, cb, cc, cn = _pts(ctr, ctr_pdim)
+    if feat is not None:
+        st = feat.stride()
+        D = feat.shape[feat_ddim]
+        fb, fd, fn = st[0], st[feat_ddim], st[feat_pdim]
+    else:
+        D, fb, fd, fn = 0, 0, 0, 0
+    ch = torch.tensor(list(chans), dtype=torch.int32)  # host array, read by the launcher only
+    pts = (ptr(xyz), sb, sc, sn, N, ptr(ctr), cb, cc, cn, S, B)
+    rest = (ptr(feat), fb, fd, fn, D, ptr(count), ptr(lst), int(nsample), len(chans) - 1, ptr(ch))
+    if dtypes:
+        fdt = dtype_code(feat) if feat is not None else _lib.F32
+        return (dtype_code(xyz),) + pts + (fdt,) + rest, (B, N, S, D), ch
+    return pts + rest, (B, N, S, D), ch
+
+
 # largest cloud the register-resident FPS kernel takes (csrc/fps.hip); beyond it a workspace
 FPS_REG_LIMIT = {torch.float32: 16384, torch.float64: 8192}
 
@@ -164,25 +196,14 @@ def sa_group_mlp(xyz, ctr, feat, count, lst, nsample, chans, params, xyz_pdim=2,
     ``feat`` is None or a (B, D, N)-indexable strided view; output (B, S, C_last) fp32.  Points
     in (B, N, 4) rows (``points_pack4``, xyz_pdim=1) are gathered one 16-byte load per row."""
     _lib.require_gpu(xyz, ctr, count, lst, params)
-    B = xyz.shape[0]
-    N, sb, sc, sn = _pts(xyz, xyz_pdim)
-    S, cb, cc, cn = _pts(ctr, ctr_pdim)
-    if feat is not None:
-        st = feat.stride()
-        D = feat.shape[feat_ddim]
-        fb, fd, fn = st[0], st[feat_ddim], st[feat_pdim]
-        fdt = dtype_code(feat)
-    else:
-        D, fb, fd, fn, fdt = 0, 0, 0, 0, _lib.F32
-    ch = torch.tensor(list(chans), dtype=torch.int32)  # host array, read by the launcher only
+    args, (B, N, S, D), ch = _sa_operands(xyz, ctr, feat, count, lst, nsample, chans, xyz_pdim, feat_ddim, feat_pdim,
+                                          ctr_pdim)
     out = torch.empty(B, S, chans[-1], dtype=torch.float32, device=xyz.device)
     macs = sum(a * b for a, b in zip(chans[:-1], chans[1:]))
     # two-layer MFMA tables take a workspace: the per-point half of layer 1 and the centre order
     ws_bytes = _lib.load().dvcp_sa_group_mlp_workspace_bytes(B, N, S, len(chans) - 1, ch.data_ptr())
     ws = torch.empty((ws_bytes + 3) // 4, dtype=torch.float32, device=xyz.device) if ws_bytes else None
-    call("dvcp_sa_group_mlp_ws", dtype_code(xyz), ptr(xyz), sb, sc, sn, N, ptr(ctr), cb, cc, cn, S, B, fdt,
-         ptr(feat), fb, fd, fn, D, ptr(count), ptr(lst), int(nsample), len(chans) - 1, ptr(ch), ptr(params), ptr(out),
-         ptr(ws), stream(),
+    call("dvcp_sa_group_mlp_ws", *args, ptr(params), ptr(out), ptr(ws), stream(),
          work=(2.0 * macs * B * S * nsample, B * S * (4 * nsample + 4 * chans[-1]) + B * N * 4 * (3 + D),
                _sa_exec_flops(chans, B, N, S, nsample, count)))
     return out
@@ -680,8 +701,7 @@ def dfe_backward(X, params, grad_out, want_input_grad=False):
     Xc = X.contiguous()
     R = Xc.numel() // (32 * 35)
     g = grad_out.reshape(R, 32).float().contiguous()
-    ws = torch.empty(max(1, int(_lib.load().dvcp_dfe_backward_workspace_bytes(R)) // 4), dtype=torch.float32,
-                     device=X.device)
+    ws = _workspace("dvcp_dfe_backward_workspace_bytes", R, device=X.device)
     gp = torch.empty(DFE_NPARAMS, dtype=torch.float32, device=X.device)
     gX = torch.empty(X.shape, dtype=torch.float32, device=X.device) if want_input_grad else None
     call("dvcp_dfe_backward", dtype_code(Xc), ptr(Xc), R, ptr(params), ptr(g), ptr(ws), ptr(gp), ptr(gX), stream())
@@ -698,10 +718,7 @@ def dfe_tgt_backward(ref_xyz, ref_feat, cand, dist, idx, params, grad_out, ref_p
     Q = cand.shape[1]
     feat_c, cand_c, dist_c, idx_c = ref_feat.contiguous(), cand.contiguous(), dist.contiguous(), idx.contiguous()
     g = grad_out.reshape(B, Q, 32).float().contiguous()
-    nbytes = int(_lib.load().dvcp_dfe_tgt_backward_workspace_bytes(B, Q, M, int(bool(want_feat_grad))))
-    if nbytes < 0:
-        raise RuntimeError("dvcp_dfe_tgt_backward_workspace_bytes: size query failed")
-    ws = torch.empty(max(1, (nbytes + 3) // 4), dtype=torch.float32, device=ref_xyz.device)
+    ws = _workspace("dvcp_dfe_tgt_backward_workspace_bytes", B, Q, M, int(bool(want_feat_grad)), device=ref_xyz.device)
     gp = torch.empty(DFE_NPARAMS, dtype=torch.float32, device=ref_xyz.device)
     gF = torch.empty(B, M, 32, dtype=torch.float32, device=ref_xyz.device) if want_feat_grad else None
     call("dvcp_dfe_tgt_backward", dtype_code(ref_xyz), ptr(ref_xyz), rb, rc, rn, M, ptr(feat_c), ptr(cand_c),
@@ -759,8 +776,7 @@ def cpg_backward(src, tgt, cand, G, params, grad_vcp):
     dev = cand.device
     gsrc = torch.empty(B, K, 32, dtype=torch.float32, device=dev)
     gtgt = torch.empty(B, K, 32, C, dtype=torch.float32, device=dev)
-    ws = torch.empty(max(1, int(_lib.load().dvcp_cpg_backward_workspace_bytes(P)) // 4), dtype=torch.float32,
-                     device=dev)
+    ws = _workspace("dvcp_cpg_backward_workspace_bytes", P, device=dev)
     gp = torch.empty(CPG_NPARAMS, dtype=torch.float32, device=dev)
     call("dvcp_cpg_backward", ptr(srcc), ptr(tgt), tgt.stride(1), tgt.stride(2), tgt.stride(3), ptr(candc), P, int(G),
          ptr(params), ptr(gv), ptr(gsrc), ptr(gtgt), ptr(ws), ptr(gp), stream(),
@@ -812,53 +828,25 @@ def sa_group_mlp_backward(xyz, ctr, feat, count, lst, nsample, chans, params, bn
     Returns (packed parameter gradient: per layer dW, db, dgamma, dbeta; dL/d feat (B, N, D) fp32
     or None)."""
     _lib.require_gpu(xyz, ctr, count, lst, params, bnstat, grad_out)
-    B = xyz.shape[0]
-    N, sb, sc, sn = _pts(xyz, xyz_pdim)
-    S, cb, cc, cn = _pts(ctr, 2)
-    if feat is not None:
-        st = feat.stride()
-        D = feat.shape[feat_ddim]
-        fb, fd, fn = st[0], st[feat_ddim], st[feat_pdim]
-        fdt = dtype_code(feat)
-    else:
-        D, fb, fd, fn, fdt = 0, 0, 0, 0, _lib.F32
-    ch = torch.tensor(list(chans), dtype=torch.int32)
-    nl = len(chans) - 1
+    args, (B, N, S, D), ch = _sa_operands(xyz, ctr, feat, count, lst, nsample, chans, xyz_pdim, feat_ddim, feat_pdim)
     npar = sum(a * b + 3 * b for a, b in zip(chans[:-1], chans[1:]))
     dev = xyz.device
-    ws = torch.empty(max(1, int(_lib.load().dvcp_sa_group_mlp_backward_workspace_bytes(B, S, nl, ch.data_ptr())) // 4),
-                     dtype=torch.float32, device=dev)
+    ws = _workspace("dvcp_sa_group_mlp_backward_workspace_bytes", B, S, len(chans) - 1, ch.data_ptr(), device=dev)
     gp = torch.empty(npar, dtype=torch.float32, device=dev)
     gF = torch.zeros(B, N, D, dtype=torch.float32, device=dev) if (want_feat_grad and D > 0) else None
     g = grad_out.float().contiguous()
-    call("dvcp_sa_group_mlp_backward", dtype_code(xyz), ptr(xyz), sb, sc, sn, N, ptr(ctr), cb, cc, cn, S, B, fdt,
-         ptr(feat), fb, fd, fn, D, ptr(count), ptr(lst), int(nsample), nl, ptr(ch), ptr(params), ptr(bnstat), ptr(g),
-         ptr(gF), ptr(ws), ptr(gp), stream())
+    call("dvcp_sa_group_mlp_backward", *args, ptr(params), ptr(bnstat), ptr(g), ptr(gF), ptr(ws), ptr(gp), stream())
     return gp, gF
 
 
 def _bn_common(xyz, ctr, feat, count, lst, nsample, chans, pack, xyz_pdim, feat_ddim, feat_pdim, workspace=True):
     """The grouping arguments shared by dvcp_sa_bn_stats / dvcp_sa_bn_backward."""
     _lib.require_gpu(xyz, ctr, count, lst, pack)
-    B = xyz.shape[0]
-    N, sb, sc, sn = _pts(xyz, xyz_pdim)
-    S, cb, cc, cn = _pts(ctr, 2)
-    if feat is not None:
-        st = feat.stride()
-        D = feat.shape[feat_ddim]
-        fb, fd, fn = st[0], st[feat_ddim], st[feat_pdim]
-        fdt = dtype_code(feat)
-    else:
-        D, fb, fd, fn, fdt = 0, 0, 0, 0, _lib.F32
-    ch = torch.tensor(list(chans), dtype=torch.int32)
-    nl = len(chans) - 1
+    args, (B, N, S, D), ch = _sa_operands(xyz, ctr, feat, count, lst, nsample, chans, xyz_pdim, feat_ddim, feat_pdim)
     ws = None
     if workspace:
-        ws_bytes = int(_lib.load().dvcp_sa_bn_workspace_bytes(B, S, nl, ch.data_ptr()))
-        ws = torch.empty(max(1, ws_bytes // 4), dtype=torch.float32, device=xyz.device)
-    args = (dtype_code(xyz), ptr(xyz), sb, sc, sn, N, ptr(ctr), cb, cc, cn, S, B, fdt, ptr(feat), fb, fd, fn, D,
-            ptr(count), ptr(lst), int(nsample), nl, ptr(ch), ptr(pack))
-    return args, ws, (B, N, S, D), ch
+        ws = _workspace("dvcp_sa_bn_workspace_bytes", B, S, len(chans) - 1, ch.data_ptr(), device=xyz.device)
+    return args + (ptr(pack),), ws, (B, N, S, D), ch
 
 
 def sa_bn_pack_floats(chans):
@@ -928,10 +916,7 @@ def sa_bn_backward(xyz, ctr, feat, count, lst, nsample, chans, pack, zrows, grad
     gF = None
     if want_feat_grad and D > 0:
         if D in (32, 64):   # per-entry rows summed per point in entry order (deterministic)
-            fb = int(_lib.load().dvcp_sa_bn_feat_workspace_bytes(B, S, int(nsample), N, D))
-            if fb < 0:
-                raise RuntimeError("dvcp_sa_bn_feat_workspace_bytes: size query failed")
-            ws = torch.empty(max(1, (fb + 3) // 4), dtype=torch.float32, device=dev)
+            ws = _workspace("dvcp_sa_bn_feat_workspace_bytes", B, S, int(nsample), N, D, device=dev)
             gF = torch.empty(B, N, D, dtype=torch.float32, device=dev)
         else:
             gF = torch.zeros(B, N, D, dtype=torch.float32, device=dev)
@@ -971,25 +956,13 @@ def sa_bnm_usable(xyz, ctr, feat, chans):
 
 def _bnm_args(xyz, ctr, feat, count, lst, nsample, chans):
     _lib.require_gpu(xyz, ctr, count, lst)
-    B = xyz.shape[0]
-    N, sb, sc, sn = _pts(xyz, 2)
-    S, cb, cc, cn = _pts(ctr, 2)
-    if feat is not None:
-        D = feat.shape[1]
-        fb, fd, fn = feat.stride(0), feat.stride(1), feat.stride(2)
-    else:
-        D, fb, fd, fn = 0, 0, 0, 0
-    ch = torch.tensor(list(chans), dtype=torch.int32)
-    return (B, N, S, D), ch, (ptr(xyz), sb, sc, sn, N, ptr(ctr), cb, cc, cn, S, B, ptr(feat), fb, fd, fn, D,
-                              ptr(count), ptr(lst), int(nsample), len(chans) - 1, ptr(ch))
+    args, dims, ch = _sa_operands(xyz, ctr, feat, count, lst, nsample, chans, dtypes=False)
+    return dims, ch, args
 
 
 def _bnm_ws(B, S, N, nsample, ch, backward, dev):
-    nb = int(_lib.load().dvcp_sa_bnm_workspace_bytes(B, S, N, int(nsample), ch.numel() - 1, ch.data_ptr(),
-                                                     int(backward)))
-    if nb < 0:
-        raise RuntimeError("dvcp_sa_bnm_workspace_bytes: size query failed")
-    return torch.empty(max(1, (nb + 3) // 4), dtype=torch.float32, device=dev)
+    return _workspace("dvcp_sa_bnm_workspace_bytes", B, S, N, int(nsample), ch.numel() - 1, ch.data_ptr(),
+                      int(backward), device=dev)
 
 
 def sa_bnm_pre(feat, chans, pack):
@@ -1064,8 +1037,7 @@ def fe_head_backward(x, params, grad):
     P = x.shape[0]
     xc = x.float().contiguous()
     g = grad.reshape(P, 32).float().contiguous()
-    ws = torch.empty(max(1, int(_lib.load().dvcp_fe_head_backward_workspace_bytes(P)) // 4), dtype=torch.float32,
-                     device=x.device)
+    ws = _workspace("dvcp_fe_head_backward_workspace_bytes", P, device=x.device)
     gp = torch.empty(32 * 64 + 32, dtype=torch.float32, device=x.device)
     gx = torch.empty(P, 64, dtype=torch.float32, device=x.device)
     call("dvcp_fe_head_backward", ptr(xc), P, ptr(params), ptr(g), ptr(gx), ptr(ws), ptr(gp), stream())
@@ -1163,10 +1135,6 @@ CPG1D_MAX_GZ = 64       # dvcp_cpg1d / dvcp_cpg1d_backward: the z line of one wa
 WEIGHTING_NPARAMS = 32 * 16 + 16 + 16 * 8 + 8 + 8 + 1   # PaperWeighting.packed_params()
 
 
-def _workspace(nbytes, device):
-    return torch.empty(max(1, (int(nbytes) + 3) // 4), dtype=torch.float32, device=device)
-
-
 def cpg1d_backward(src, tgt, cand, params, grad_vcp, want_src=True, want_tgt=True):
     """Gradients of ``cpg1d`` (paper Sec. 3.6): (d src (B, K, 32) or None, d tgt (B, K, Gz, 32) or None,
     d params (dvcp_cpg1d_nparams())), the parameter gradient summed in a fixed order."""
@@ -1183,7 +1151,7 @@ def cpg1d_backward(src, tgt, cand, params, grad_vcp, want_src=True, want_tgt=Tru
     gsrc = torch.empty(B, K, 32, dtype=torch.float32, device=dev) if want_src else None
     gtgt = torch.empty(B, K, Gz, 32, dtype=torch.float32, device=dev) if want_tgt else None
     gp = torch.empty(int(_lib.load().dvcp_cpg1d_nparams()), dtype=torch.float32, device=dev)
-    ws = _workspace(_lib.load().dvcp_cpg1d_backward_workspace_bytes(P), dev)
+    ws = _workspace("dvcp_cpg1d_backward_workspace_bytes", P, device=dev)
     macs = 3 * (32 * 16 + 16 * 4 + 4) * P * Gz
     call("dvcp_cpg1d_backward", ptr(s), ptr(t), ptr(c), P, Gz, ptr(params), ptr(gv), ptr(gsrc), ptr(gtgt), ptr(ws),
          ws.numel() * 4, ptr(gp), stream(),
@@ -1205,7 +1173,7 @@ def weighting_backward(feat, params, grad_score, want_feat=True):
     g = grad_score.reshape(P).float().contiguous()
     gfeat = torch.empty(P, 32, dtype=torch.float32, device=dev) if want_feat else None
     gp = torch.empty(WEIGHTING_NPARAMS, dtype=torch.float32, device=dev)
-    ws = _workspace(_lib.load().dvcp_weighting_backward_workspace_bytes(P), dev)
+    ws = _workspace("dvcp_weighting_backward_workspace_bytes", P, device=dev)
     macs = (32 * 16 + 16 * 8 + 8) * P
     call("dvcp_weighting_backward", ptr(feat), P, ptr(params), ptr(g), ptr(gfeat), ptr(ws), ws.numel() * 4, ptr(gp),
          stream(), work=(2.0 * macs * (3 if want_feat else 2), 4.0 * P * (32 + 1 + (32 if want_feat else 0))))
@@ -1232,7 +1200,7 @@ def weighting_bn_stats(feat, params, layer):
     P = _wbn_rows("weighting_bn_stats", feat, params)
     C = {1: 16, 2: 8}[int(layer)]
     sums = torch.empty(2, C, dtype=torch.float64, device=feat.device)
-    ws = _workspace(_lib.load().dvcp_weighting_bn_stats_workspace_bytes(P), feat.device)
+    ws = _workspace("dvcp_weighting_bn_stats_workspace_bytes", P, device=feat.device)
     macs = (32 * 16 + (16 * 8 if layer == 2 else 0)) * P
     call("dvcp_weighting_bn_stats", ptr(feat), P, ptr(params), int(layer), ptr(ws), ws.numel() * 4, ptr(sums),
          stream(), work=(2.0 * macs, 4.0 * P * 32))
@@ -1262,7 +1230,7 @@ def weighting_bn_backward(feat, params, bnstat, grad_score, mode, want_feat=True
                            f"gradients, got {bnstat.numel()} and {grad_score.numel()}")
     dev = feat.device
     g = grad_score.reshape(P).float().contiguous()
-    ws = _workspace(_lib.load().dvcp_weighting_bn_backward_workspace_bytes(P), dev)
+    ws = _workspace("dvcp_weighting_bn_backward_workspace_bytes", P, device=dev)
     macs = (32 * 16 + 16 * 8 + 8) * P
     if mode:
         sums = torch.empty(2, {1: 16, 2: 8}[int(mode)], dtype=torch.float64, device=dev)
@@ -1290,39 +1258,22 @@ def feature_propagation_backward(xyz1, xyz2, p2_rows, p1, chans, relu, params, b
     weights and the layer chain are recomputed (nothing is saved by the forward); identical calls give
     identical bits."""
     _lib.require_gpu(xyz1, xyz2, p2_rows, params, bnstat, grad_out)
-    B = xyz1.shape[0]
-    N1, x1b, x1c, x1n = _pts(xyz1, 2)
-    N2, x2b, x2c, x2n = _pts(xyz2, 2)
-    if p2_rows.dtype != torch.float32 or p2_rows.stride(2) != 1:
-        raise ValueError("feature_propagation_backward: p2 rows must be fp32 with contiguous channels")
-    D2 = p2_rows.shape[2]
-    if p1 is not None:
-        if p1.dtype != torch.float32:
-            p1 = p1.float()
-        D1, (p1b, p1d, p1n) = p1.shape[1], p1.stride()
-    else:
-        D1, p1b, p1d, p1n = 0, 0, 0, 0
     chans = list(chans)
+    args, (B, N1, N2, D1, D2), keep = _fp_operands("feature_propagation_backward", xyz1, xyz2, p2_rows, p1, chans, relu)
     if grad_out.numel() != B * N1 * chans[-1]:
         raise RuntimeError(f"feature_propagation_backward: grad_out {tuple(grad_out.shape)} is not "
                            f"({B}, {N1}, {chans[-1]})")
     dev = xyz1.device
-    ch = torch.tensor(chans, dtype=torch.int32)
-    rl = torch.tensor([int(bool(r)) for r in relu], dtype=torch.int32)
     g = grad_out.reshape(B, N1, chans[-1]).float().contiguous()
     want_p1 = bool(want_p1) and D1 > 0
     gp = torch.empty(fp_nparams(chans), dtype=torch.float32, device=dev)
     gp1 = torch.empty(B, N1, D1, dtype=torch.float32, device=dev) if want_p1 else None
     gp2 = torch.empty(B, N2, D2, dtype=torch.float32, device=dev) if want_p2 else None
-    nbytes = int(_lib.load().dvcp_feature_propagation_backward_workspace_bytes(B, N1, N2, D2, len(chans) - 1,
-                                                                               ch.data_ptr(), int(bool(want_p2))))
-    if nbytes < 0:
-        raise RuntimeError("dvcp_feature_propagation_backward_workspace_bytes: size query failed")
-    ws = _workspace(nbytes, dev)
+    ws = _workspace("dvcp_feature_propagation_backward_workspace_bytes", B, N1, N2, D2, len(chans) - 1,
+                    keep[0].data_ptr(), int(bool(want_p2)), device=dev)
     macs = sum(a * b for a, b in zip(chans[:-1], chans[1:]))
-    call("dvcp_feature_propagation_backward", ptr(xyz1), x1b, x1c, x1n, N1, ptr(xyz2), x2b, x2c, x2n, N2, B, ptr(p1),
-         p1b, p1d, p1n, D1, ptr(p2_rows), p2_rows.stride(0), p2_rows.stride(1), D2, len(chans) - 1, ptr(ch), ptr(rl),
-         ptr(params), ptr(bnstat), ptr(g), ptr(gp1), ptr(gp2), ptr(ws), ws.numel() * 4, ptr(gp), stream(),
+    call("dvcp_feature_propagation_backward", *args, ptr(params), ptr(bnstat), ptr(g), ptr(gp1), ptr(gp2), ptr(ws),
+         ws.numel() * 4, ptr(gp), stream(),
          work=(B * N1 * (9.0 * N2 + 2.0 * macs * (3 if (want_p1 or want_p2) else 2)),
                4.0 * B * (3 * (N1 + N2) + N2 * D2 + N1 * (D1 + chans[-1]) + (N1 * D1 if want_p1 else 0)
                           + (N1 * 3 * D2 * 2 + N2 * D2 if want_p2 else 0))))
@@ -1358,7 +1309,7 @@ def feature_propagation_bn_stats(xyz1, xyz2, p2_rows, p1, chans, relu, params, l
     chans = list(chans)
     args, (B, N1, N2, D1, D2), keep = _fp_operands("feature_propagation_bn_stats", xyz1, xyz2, p2_rows, p1, chans, relu)
     sums = torch.empty(2, chans[layer], dtype=torch.float64, device=xyz1.device)
-    ws = _workspace(_lib.load().dvcp_feature_propagation_bn_stats_workspace_bytes(B, N1), xyz1.device)
+    ws = _workspace("dvcp_feature_propagation_bn_stats_workspace_bytes", B, N1, device=xyz1.device)
     macs = sum(a * b for a, b in zip(chans[:layer], chans[1:layer + 1]))
     call("dvcp_feature_propagation_bn_stats", *args, ptr(params), int(layer), ptr(ws), ws.numel() * 4, ptr(sums),
          stream(), work=(B * N1 * (9.0 * N2 + 2.0 * macs), 4.0 * B * (3 * (N1 + N2) + N2 * D2 + N1 * D1)))
@@ -1385,11 +1336,8 @@ def feature_propagation_bn_backward(xyz1, xyz2, p2_rows, p1, chans, relu, params
     g = grad_out.reshape(B, N1, chans[-1]).float().contiguous()
     want_p1 = bool(want_p1) and D1 > 0 and mode == 0
     want_p2 = bool(want_p2) and mode == 0
-    nbytes = int(_lib.load().dvcp_feature_propagation_bn_backward_workspace_bytes(B, N1, N2, D2, len(chans) - 1,
-                                                                                  keep[0].data_ptr(), int(want_p2)))
-    if nbytes < 0:
-        raise RuntimeError("dvcp_feature_propagation_bn_backward_workspace_bytes: size query failed")
-    ws = _workspace(nbytes, dev)
+    ws = _workspace("dvcp_feature_propagation_bn_backward_workspace_bytes", B, N1, N2, D2, len(chans) - 1,
+                    keep[0].data_ptr(), int(want_p2), device=dev)
     macs = sum(a * b for a, b in zip(chans[:-1], chans[1:]))
     work = (B * N1 * (9.0 * N2 + 2.0 * macs * (3 if (want_p1 or want_p2) else 2)),
             4.0 * B * (3 * (N1 + N2) + N2 * D2 + N1 * (D1 + chans[-1])))
@@ -1418,10 +1366,7 @@ def group_rows_backward(count, lst, nsample, N, grad_rows):
     D = grad_rows.shape[3] - 3
     g = grad_rows.float().contiguous()
     gfeat = torch.empty(B, int(N), D, dtype=torch.float32, device=g.device)
-    nbytes = int(_lib.load().dvcp_group_rows_backward_workspace_bytes(B, Q, int(N), int(nsample)))
-    if nbytes < 0:
-        raise RuntimeError("dvcp_group_rows_backward_workspace_bytes: size query failed")
-    ws = _workspace(nbytes, g.device)
+    ws = _workspace("dvcp_group_rows_backward_workspace_bytes", B, Q, int(N), int(nsample), device=g.device)
     call("dvcp_group_rows_backward", ptr(count), ptr(lst), ns_list, int(nsample), Q, int(N), D, B, ptr(g), ptr(gfeat),
          ptr(ws), ws.numel() * 4, stream(),
          work=(1.0 * B * Q * nsample * D, 4.0 * B * (Q * nsample * (D + 3) + N * D)))

@@ -550,7 +550,7 @@ int64_t dvcp_weighting_backward_workspace_bytes(int P);
 int dvcp_weighting_backward(const float* feat, int P, const float* params, const float* grad_score,
                             float* grad_feat, void* workspace, int64_t ws_bytes, float* grad_params,
                             void* stream);
-/* The paper's weighting layer under batch-statistics BatchNorm (training mode; csrc/paper_wl_bn.hip).
+/* The paper's weighting layer under batch-statistics BatchNorm (training mode; csrc/paper_wl_train.hip).
  * The three entry points share one arithmetic, y = (W x + b) * scale + shift, a = y > 0 ? y : 0 per BN
  * layer, on params = W1 (16 x 32) | b1 | scale1 | shift1 | W2 (8 x 16) | b2 | scale2 | shift2 | W3 (8)
  * | b3: dvcp_weighting_bn_nparams() = 721 floats.  feat: P x 32 fp32.  No BN fold: gamma = 0 is

@@ -1,5 +1,5 @@
 """Paper mode under batch-statistics BatchNorm (``bn_train=True`` and ``.train()``): the weighting
-layer's own entry points (dvcp_weighting_bn_stats / _forward / _backward, csrc/paper_wl_bn.hip)
+layer's own entry points (dvcp_weighting_bn_stats / _forward / _backward, csrc/paper_wl_train.hip)
 against the checker's PaperWeighting in train mode (oracle/paper.py, fp64); the paper's first set
 abstraction (3[+3] -> 32 -> 32) through ``batchnorm.train_forward`` / ``train_backward`` against the
 checker's PointNetSetAbstraction in train mode; and DeepVCPPaper(train_heads=True, bn_train=True) after
@@ -262,6 +262,33 @@ def test_weighting_bn_edges(cuda):
     assert list(plain.state_dict()) == list(mine.state_dict())
     with pytest.raises(NotImplementedError, match="training mode"):
         plain.train()(c["feat"].to(cuda))
+
+
+@pytest.mark.parametrize("P", [1, 65])   # one row; a full 64-row tile and a one-row tile
+def test_weighting_backward_eval_and_identity_bn_same_bits(cuda, P):
+    """The eval and the batch-statistics instance of the one backward kernel on the same numbers: the
+    eval pack of unfolded fc1-fc3, and the train pack with scale = 1, shift = 0 under mean = 0, rstd = 1,
+    A/M = B/M = 0.  The BN path then computes z * 1 + 0 and 1 * ((g - 0) - xhat * 0), which reproduce z
+    and g exactly up to the sign of a zero, so every gradient is equal (torch.equal ignores that sign)."""
+    from dvcp import ops
+    gen = torch.Generator().manual_seed(700 + P)
+    w1, b1 = torch.randn(16, 32, generator=gen) * 0.3, torch.randn(16, generator=gen)
+    w2, b2 = torch.randn(8, 16, generator=gen) * 0.3, torch.randn(8, generator=gen)
+    w3, b3 = torch.randn(8, generator=gen) * 0.3, torch.randn(1, generator=gen)
+    feat = torch.randn(P, 32, generator=gen).to(cuda)
+    g = torch.randn(P, generator=gen).to(cuda)
+    eval_pack = torch.cat([w1.reshape(-1), b1, w2.reshape(-1), b2, w3, b3]).to(cuda)
+    train_pack = torch.cat([w1.reshape(-1), b1, torch.ones(16), torch.zeros(16), w2.reshape(-1), b2, torch.ones(8),
+                            torch.zeros(8), w3, b3]).to(cuda)
+    assert eval_pack.numel() == ops.WEIGHTING_NPARAMS and train_pack.numel() == ops.WEIGHTING_BN_NPARAMS
+    bnstat = torch.zeros(ops.WEIGHTING_BN_NSTAT, dtype=torch.float64, device=cuda)
+    bnstat[16:32] = 1.0            # bn1: mean | rstd | A/M | B/M, 16 each
+    bnstat[64 + 8:64 + 16] = 1.0   # bn2: the same, 8 each
+    gp_e, gf_e = ops.weighting_backward(feat, eval_pack, g)
+    gp_b, gf_b = ops.weighting_bn_backward(feat, train_pack, bnstat, g, 0)
+    assert float(gp_e.abs().max()) > 0.0   # d b3 = sum g softplus'(v) at the least
+    assert torch.equal(gp_e, gp_b)
+    assert torch.equal(gf_e, gf_b)
 
 
 # ------------------------------------------------------------- the paper's sa1, batch statistics
