@@ -7,48 +7,30 @@
 //
 // Plan (G <= 11, C <= 1331), one 1024-thread workgroup per key point: the key point's (C, 32)
 // target block is loaded once into registers; the cost volume is built in LDS one 8-channel
-// quarter at a time with a zero halo (13^3 cells, 70 KB) next to conv1's weights ([ci][tap][co],
-// 55 KB); conv1 runs on the matrix cores (see below), accumulating the quarters in registers;
+// quarter at a time with a zero halo (13^3 cells, three bf16 piece images, 103 KB) next to the
+// quarter's conv1 weights (21 KB); conv1 runs on the matrix cores (see below), accumulating the
+// quarters in registers;
 // its output (haloed) then replaces volume and weights in LDS for conv2 (VALU: its 4 output
 // channels would fill a quarter of an MFMA tile); conv2's haloed output feeds conv3 (VALU,
 // maskless), and the softmax and weighted mean finish in registers.
+//
+// conv1 runs on the bf16 matrix cores (v_mfma_f32_16x16x32_bf16) through the fp32-accurate
+// three-way split of split3.h: each 8-channel quarter of the cost volume is stored in LDS as three
+// bf16 piece images ([piece][cell][8 channels], 16 B per cell and piece, split once when the volume
+// is built) and each quarter's weights as three B-fragment images; a k-step covers 4 taps x 8
+// channels (K = 32), 7 k-steps per quarter (taps 0..26 + one zero tap), six bf16 MFMAs (16 cycles)
+// each.
+//
+// conv2 takes the 48 (ci, kd) planes of scalar weights in turn, each loaded at once, the second
+// voxel chosen per wave.  Measured and not kept: the next plane's weights prefetched into a second
+// SGPR set (spills to VGPR lanes), and W2 transposed into LDS read as broadcast float4 per tap
+// (0.249 ms against 0.231: the LDS pipe bounds it), the same with a register prefetch 0.287 ms
+// (DESIGN.md section 4 has the history of the tap loop and the fp32 conv1 this kernel replaced).
 #include "common.h"
 #include "cpg_grid.h"
 #include "split3.h"
 
 namespace dvcp {
-
-
-// DVCP_CPG_SPLIT3 (default): conv1 on the bf16 matrix cores (v_mfma_f32_16x16x32_bf16) with the
-// fp32-accurate three-way split of sa_mfma_common.h: each 8-channel quarter of the cost volume is
-// stored in LDS as three bf16 piece images ([piece][cell][8 channels], 16 B per cell and piece,
-// split once when the volume is built) and each quarter's weights as three B-fragment images; a
-// k-step covers 4 taps x 8 channels (K = 32), 7 k-steps per quarter (taps 0..26 + one zero tap),
-// six bf16 MFMAs (16 cycles) each, instead of 27 x 2 fp32 16x16x4 MFMAs (32 cycles) per quarter.
-#ifndef DVCP_CPG_SPLIT3
-#define DVCP_CPG_SPLIT3 1
-#endif
-// DVCP_CPG_C2: conv2's loop.  2 (default): (ci, kd) planes of scalar weights loaded at once, the
-// second voxel chosen per wave; 1: the round-4 tap loop (a scalar load, a divergent branch and an
-// LDS + scalar-cache wait per tap).  C3 (8 x 64 key points), A/B on one box: 0.249 / 0.250 ->
-// 0.231 / 0.230 ms, conv2's phase 80.5k -> 52.5k clk and scratch 8 -> 0 B.  Measured and not kept:
-// the next plane's weights prefetched into a second SGPR set (spills to VGPR lanes), and W2
-// transposed into LDS read as broadcast float4 per tap (0.249 ms: the LDS pipe bounds it), the
-// same with a register prefetch 0.287 ms (profiles/round5/r5v_cpg_ab.log, r5x_cpg_ab.log).
-#ifndef DVCP_CPG_C2
-#define DVCP_CPG_C2 2
-#endif
-
-// conv1 runs on the bf16 matrix cores through the three-way split of csrc/split3.h
-
-// DVCP_CPG_DIAG (diagnostic builds only): wave 0 of each workgroup records the shader clock at the
-// phase boundaries and writes the deltas over the key point's softmax weights (tools/cpg_diag.py).
-#ifdef DVCP_CPG_DIAG
-#define DVCP_CPG_TICK(k) \
-  if (tid == 0) dg[k] = __builtin_readcyclecounter();
-#else
-#define DVCP_CPG_TICK(k)
-#endif
 
 constexpr int kCpgThreads = 1024;  // 16 waves: four per SIMD (LDS allows one workgroup per CU)
 constexpr int kCpgMaxC = 1331;
@@ -56,11 +38,8 @@ constexpr int kCpgMaxG = 11;
 constexpr int kCpgV = (kCpgMaxC + kCpgThreads - 1) / kCpgThreads;  // voxels per thread (conv2/3)
 constexpr int kCpgPV = (kCpgMaxG + 2) * (kCpgMaxG + 2) * (kCpgMaxG + 2);  // haloed voxels (13^3)
 constexpr int kCpgQ = 8;                                                  // channels per quarter
-constexpr int kCpgVolF = kCpgQ * kCpgPV;                                  // haloed quarter volume
-constexpr int kCpgW1F = 32 * 27 * 16;
-constexpr int kCpgBigF = 16 * kCpgPV;  // quarter volume + conv1 weights, later haloed conv1 / conv2 outputs
+constexpr int kCpgBigF = 16 * kCpgPV;  // split quarter volume + conv1 weights, later haloed conv1 / conv2 outputs
 constexpr int kCpgE = (32 * kCpgMaxC + kCpgThreads - 1) / kCpgThreads;  // target values per thread
-static_assert(kCpgVolF + kCpgW1F <= kCpgBigF, "quarter volume + conv1 weights must fit the area");
 
 // Each 8-channel quarter of the cost volume takes the target values l = 32 g + f' with f' in the
 // quarter (Q11: l = f C + c).  QBAL (every residue c mod 32 has exactly 8 channels f per quarter,
@@ -91,20 +70,10 @@ __global__ __launch_bounds__(kCpgThreads) void cpg_kernel(const float* __restric
   __shared__ float bias[16 + 4 + 1];
   __shared__ float sv[32];
   __shared__ float red[32];
-#if !DVCP_CPG_SPLIT3
-  float* vol = big;            // conv1 input: a haloed 8-channel quarter of the cost volume
-  float* w1 = big + kCpgVolF;  // conv1 W [ci][tap][co]
-#endif
   float* out1 = big;           // after conv1: its output, haloed [co][cell] (16 x PV)
   float* out2 = big;           // after conv2: its output, haloed [co][cell] (4 x PV)
 
   const int p = blockIdx.x, tid = threadIdx.x;
-#ifdef DVCP_CPG_DIAG
-  uint64_t dg[16];
-#pragma unroll
-  for (int i = 0; i < 16; ++i) dg[i] = 0;
-#endif
-  DVCP_CPG_TICK(0)
   const int C = G * G * G, GG = G * G;
   const int PG = G + 2, PGG = PG * PG, PV = PG * PGG;
   const FastDiv dG(G), dGG(GG);
@@ -141,30 +110,23 @@ __global__ __launch_bounds__(kCpgThreads) void cpg_kernel(const float* __restric
       tv[u] = e < 32 * C ? T[(e % 32) * t_f + (e / 32) * t_c] : 0.f;
     }
   }
-#if !DVCP_CPG_SPLIT3
-#pragma unroll 6
-  for (int i = tid; i < 16 * 32 * 27; i += kCpgThreads) {  // torch (co, ci, kd, kh, kw)
-    const int co = i / (32 * 27), r = i % (32 * 27);
-    w1[r * 16 + co] = P1[i];
-  }
-#endif
   if (tid < 4 * 27) w3[tid] = P3[tid];
   if (tid < 16) bias[tid] = P1[16 * 32 * 27 + tid];
   if (tid < 4) bias[16 + tid] = P2[4 * 16 * 27 + tid];
   if (tid == 0) bias[20] = P3[4 * 27];
   if (tid < 32) sv[tid] = src[static_cast<int64_t>(p) * 32 + tid];
 
-  DVCP_CPG_TICK(1)
   // per-thread voxels (conv3, softmax)
   int gv[kCpgV];
 #pragma unroll
   for (int v = 0; v < kCpgV; ++v) gv[v] = tid + v * kCpgThreads;
 
-  // conv1 (32 -> 16, k3) as an implicit GEMM on v_mfma_f32_16x16x4_f32: rows = 16-voxel tiles,
-  // k = 4 input channels at one tap, columns = the 16 output channels.  Wave w owns tiles
-  // w, w + 8, ... with their accumulators in registers: each k-step is one B fragment (weights)
-  // and up to kTW independent MFMAs.  The input is haloed (zero border), so a tap is a constant
-  // address shift and needs no mask; lane reads voxel 16 t + (lane & 15), channel 4 cg + (lane >> 4).
+  // conv1 (32 -> 16, k3) as an implicit GEMM on v_mfma_f32_16x16x32_bf16: rows = 16-voxel tiles,
+  // k = 4 taps x the quarter's 8 input channels, columns = the 16 output channels.  Wave w owns
+  // tiles w, w + 16, ... with their accumulators in registers: each k-step is one B fragment
+  // (weights, three pieces) and up to kTW independent split-3 products.  The input is haloed (zero
+  // border), so a tap is a constant address shift and needs no mask; lane reads voxel
+  // 16 t + (lane & 15) at tap 4 st + (lane >> 4), all 8 channels of the quarter.
   constexpr int kT = (kCpgMaxC + 15) / 16;          // voxel tiles at C = 1331
   constexpr int kW = kCpgThreads / 64;
   constexpr int kTW = (kT + kW - 1) / kW;           // per wave
@@ -181,7 +143,6 @@ __global__ __launch_bounds__(kCpgThreads) void cpg_kernel(const float* __restric
 #pragma unroll
   for (int i = 0; i < kTW; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-#if DVCP_CPG_SPLIT3
   {
     uint4* vsp = reinterpret_cast<uint4*>(big);                    // [piece][cell]: 8 bf16 channels
     uint4* w1p = vsp + 3 * PV;                                     // [k-step][piece][lane]
@@ -189,7 +150,6 @@ __global__ __launch_bounds__(kCpgThreads) void cpg_kernel(const float* __restric
 #pragma unroll 1
     for (int q = 0; q < 32 / kCpgQ; ++q) {
       __syncthreads();
-      DVCP_CPG_TICK(2 + 3 * q)
       for (int i = tid; i < 3 * PV; i += kCpgThreads) vsp[i] = make_uint4(0u, 0u, 0u, 0u);
       // this quarter's conv1 weights: k-step s, lane (co = l & 15, tap 4 s + (l >> 4)), channel j
       for (int i = tid; i < 7 * 64; i += kCpgThreads) {
@@ -209,8 +169,10 @@ __global__ __launch_bounds__(kCpgThreads) void cpg_kernel(const float* __restric
         w1p[(st * 3 + 2) * 64 + l] = __builtin_bit_cast(uint4, b2);
       }
       __syncthreads();
-      DVCP_CPG_TICK(3 + 3 * q)
-      // cost volume quarter as bf16 pieces (see the fp32 path below for the Q11 index map)
+      // cost volume quarter as bf16 pieces: channels f' in [8q, 8q + 8) of
+      // cost[f'][g] = (src[f'] - T[l])^2, l = g*32 + f' = f*C + c (the reference's reshape, Q11).
+      // (The opaque zero keeps the compiler from hoisting the addresses of every value of the
+      // thread out of the quarter loop into registers.)
       int zo = 0;
       asm volatile("" : "+v"(zo));
       uint16_t* vh = reinterpret_cast<uint16_t*>(vsp);
@@ -239,6 +201,8 @@ __global__ __launch_bounds__(kCpgThreads) void cpg_kernel(const float* __restric
           }
         }
       } else {
+        // element e = u*kCpgThreads + tid of the block is (c = e / 32, f = e % 32): f is fixed per
+        // thread (kCpgThreads % 32 == 0) and c advances by kCpgThreads / 32 per u, and so does l = f*C + c.
         const int f0 = tid & 31;
         const int l0 = f0 * C + (tid >> 5) + zo;
 #pragma unroll
@@ -249,7 +213,6 @@ __global__ __launch_bounds__(kCpgThreads) void cpg_kernel(const float* __restric
         }
       }
       __syncthreads();
-      DVCP_CPG_TICK(4 + 3 * q)
 #pragma unroll 1
       for (int st = 0; st < 7; ++st) {
         // lane's tap 4 st + kg (tap 27: zero weights, any in-range cell)
@@ -270,50 +233,7 @@ __global__ __launch_bounds__(kCpgThreads) void cpg_kernel(const float* __restric
       }
     }
   }
-#else
-#pragma unroll 1
-  for (int q = 0; q < 32 / kCpgQ; ++q) {
-    __syncthreads();
-    for (int i = tid; i < kCpgQ * PV; i += kCpgThreads) vol[i] = 0.f;
-    __syncthreads();
-    // cost volume quarter: channels f' in [8q, 8q + 8) of cost[f'][g] = (src[f'] - T[l])^2,
-    // l = g*32 + f' = f*C + c (the reference's reshape, Q11).  (The opaque zero keeps the
-    // compiler from hoisting 84 addresses per thread out of the quarter loop into registers.)
-    int zo = 0;
-    asm volatile("" : "+v"(zo));
-    // element e = u*kCpgThreads + tid of the block is (c = e / 32, f = e % 32): f is fixed per
-    // thread (kCpgThreads % 32 == 0) and c advances by kCpgThreads / 32 per u, and so does l = f*C + c.
-    const int f0 = tid & 31;
-    const int l0 = f0 * C + (tid >> 5) + zo;
-#pragma unroll
-    for (int u = 0; u < kCpgE; ++u) {
-      const int e = u * kCpgThreads + tid;
-      const int l = l0 + (kCpgThreads / 32) * u;
-      const int g = l >> 5, fp = l & 31;
-      if (e < 32 * C && (fp >> 3) == q) {
-        const float d = sv[fp] - tv[u];
-        vol[(fp & 7) * PV + cpg_halo(g, dG, dGG, PG, PGG)] = d * d;
-      }
-    }
-    __syncthreads();
-#pragma unroll 1
-    for (int t = 0; t < 27; ++t) {
-      const int off = (t / 9 - 1) * PGG + ((t / 3) % 3 - 1) * PG + (t % 3 - 1);
-#pragma unroll
-      for (int cg = 0; cg < kCpgQ / 4; ++cg) {
-        const int ci = 4 * cg + kg;  // channel within the quarter
-        const float bw = w1[((kCpgQ * q + ci) * 27 + t) * 16 + l16];
-        const float* vin = vol + ci * PV + off;
-#pragma unroll
-        for (int i = 0; i < kTW; ++i)
-          if (wave + kW * i < NT)  // wave-uniform
-            acc[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(vin[vx[i]], bw, acc[i], 0, 0, 0);
-      }
-    }
-  }
-#endif
   __syncthreads();
-  DVCP_CPG_TICK(14)
   // conv1 output -> out1 (haloed, zero border); accumulator register r of lane l is voxel
   // 16 t + 4 (l >> 4) + r, output channel l & 15
   for (int i = tid; i < 16 * PV; i += kCpgThreads) out1[i] = 0.f;
@@ -331,7 +251,6 @@ __global__ __launch_bounds__(kCpgThreads) void cpg_kernel(const float* __restric
 
   // conv2 (16 -> 4) on VALU, one voxel per thread: a 16-column MFMA tile would leave 12 of its
   // 16 output columns empty (4x the MFMA time of the useful work).
-  DVCP_CPG_TICK(15)
   int hv[kCpgV];
 #pragma unroll
   for (int v = 0; v < kCpgV; ++v) hv[v] = cpg_halo(gv[v] < C ? gv[v] : 0, dG, dGG, PG, PGG);
@@ -340,7 +259,6 @@ __global__ __launch_bounds__(kCpgThreads) void cpg_kernel(const float* __restric
   for (int v = 0; v < kCpgV; ++v)
 #pragma unroll
     for (int co = 0; co < 4; ++co) o2[v][co] = 0.f;
-#if DVCP_CPG_C2 == 2
   // The 48 (ci, kd) planes in turn; a plane's 36 weights W2[co][ci][kd][.][.] (9 contiguous floats
   // per co) are loaded at once (four s_load_dwordx8 + four dwords), one scalar-cache wait per plane
   // instead of one per tap.  A wave runs its second voxel (tid + 1024 < C: waves 0..4 at C = 1331)
@@ -384,39 +302,7 @@ __global__ __launch_bounds__(kCpgThreads) void cpg_kernel(const float* __restric
     else
       planes(std::false_type{});
   }
-#else
-  // W2[co][ci][tap] comes through the scalar cache (wave-uniform), one tap plane (4 x 9 weights)
-  // at a time.
-#pragma unroll 1
-  for (int ci = 0; ci < 16; ++ci) {
-    const float* xin = out1 + ci * PV;
-#pragma unroll
-    for (int kd = 0; kd < 3; ++kd) {
-      // (an opaque zero ordered after the running sums keeps all 108 weights of the channel from
-      // being loaded into SGPRs at once)
-      int zw = 0;
-      asm volatile("" : "+s"(zw) : "v"(o2[0][0]));
-      const float* w2c = P2 + ci * 27 + 9 * kd + zw;
-#pragma unroll
-      for (int t9 = 0; t9 < 9; ++t9) {
-        const int t = 9 * kd + t9;
-        const int off = (t / 9 - 1) * PGG + ((t / 3) % 3 - 1) * PG + (t % 3 - 1);
-#pragma unroll
-        for (int v = 0; v < kCpgV; ++v) {
-          if (v == 0 || gv[v] < C) {  // (v = 0: every thread, C >= 1024 or a clamped in-range cell)
-            const float x = xin[hv[v] + off];
-#pragma unroll
-            for (int co = 0; co < 4; ++co) o2[v][co] = __fmaf_rn(w2c[co * 16 * 27 + t9], x, o2[v][co]);
-          }
-        }
-      }
-    }
-  }
-#endif
   __syncthreads();  // every conv1 output read; out2 overwrites them
-#ifdef DVCP_CPG_DIAG
-  uint64_t dg_c2 = __builtin_readcyclecounter();
-#endif
   for (int i = tid; i < 4 * PV; i += kCpgThreads) out2[i] = 0.f;
   __syncthreads();
 #pragma unroll
@@ -471,22 +357,6 @@ __global__ __launch_bounds__(kCpgThreads) void cpg_kernel(const float* __restric
   sx = block_sum(sx, red);
   sy = block_sum(sy, red);
   sz = block_sum(sz, red);
-#ifdef DVCP_CPG_DIAG
-  if (tid == 0 && weight) {  // phase deltas: [load, q0 zero, q0 build, q0 mfma, ..., out1, conv2, rest]
-    const uint64_t end = __builtin_readcyclecounter();
-    float* o = weight + static_cast<int64_t>(p) * C;
-    o[0] = static_cast<float>(dg[1] - dg[0]);
-    for (int q = 0; q < 4; ++q) {
-      o[1 + 3 * q] = static_cast<float>(dg[3 + 3 * q] - dg[2 + 3 * q]);
-      o[2 + 3 * q] = static_cast<float>(dg[4 + 3 * q] - dg[3 + 3 * q]);
-      o[3 + 3 * q] = static_cast<float>((q < 3 ? dg[5 + 3 * q] : dg[14]) - dg[4 + 3 * q]);
-    }
-    o[13] = static_cast<float>(dg[15] - dg[14]);
-    o[14] = static_cast<float>(dg_c2 - dg[15]);
-    o[15] = static_cast<float>(end - dg_c2);
-    o[16] = static_cast<float>(end - dg[0]);
-  }
-#endif
   if (tid == 0) {
     vcp[static_cast<int64_t>(p) * 3 + 0] = sx / sw;
     vcp[static_cast<int64_t>(p) * 3 + 1] = sy / sw;

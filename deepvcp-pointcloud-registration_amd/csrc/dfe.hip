@@ -11,19 +11,11 @@
 // One thread = one neighbour row, 8 queries x 32 rows = 256 threads per workgroup.  Weights
 // are wave-uniform scalar loads; the max over a query's 32 rows goes through LDS.
 #include "common.h"
+#include "dfe_mfma.h"  // the target side on the matrix cores: launch_dfe_tgt_mfma
 
 #include <algorithm>
 
 namespace dvcp {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-// dfe_mfma.hip: the target side on fp32 MFMA.  literal = false: the three linear layers collapsed
-// into one map (default); true: fc1, fc2, fc3 evaluated one after the other.
-template <typename T>
-int launch_dfe_tgt_mfma(PointsView<T> ref, const float* feat, int M, const float* cand, const float* dist,
-                        const int32_t* idx, int B, int Q, const float* params, float* out, bool literal,
-                        hipStream_t st);
 
 // segsum.hip: deterministic per-row sums of keyed 32-float contribution rows.
 int64_t segment_sum_workspace_bytes(int64_t E, int64_t nrows);

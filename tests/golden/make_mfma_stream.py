@@ -4,7 +4,7 @@ Run once on the GPU at the commit whose arithmetic is the yardstick:
 
     python tests/golden/make_mfma_stream.py [out.npz]   # default: tests/golden/mfma_stream.npz
 
-The kernels of csrc/sa_mfma_*.hip, csrc/dfe_mfma.hip and csrc/cpg.hip feed the bf16 matrix cores
+The kernels of csrc/sa_mfma_*.hip, csrc/dfe_tgt.hip and csrc/cpg.hip feed the bf16 matrix cores
 with three-piece splits of fp32 values; a change of their instruction stream must leave every
 output bit as it was.  This module builds the seeded inputs (shared with the test, which imports
 it) and records the outputs of

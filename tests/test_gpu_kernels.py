@@ -1183,6 +1183,29 @@ def test_dfe_tgt_fp16_features(cuda, f64):
         ops.dfe_tgt(ref_xyz, half, qry, dist, idx, mine.packed_params(), ref_pdim=1, literal=True)
 
 
+def test_dfe_tgt_fp16_features_unpacked_fp32_points(cuda):
+    """dvcp_dfe_tgt_f16 on fp32 points left in the strided (B, 3, M) layout (ops.dfe_tgt always packs
+    them, so only a direct call reaches the launcher's fp16 branch without (x, y, z, 0) rows): equal
+    bit for bit to dvcp_dfe_tgt on the same points and the fp32 table holding the widened values."""
+    import dvcp
+    from dvcp import _lib, ops
+    from dvcp.ops import ptr, stream
+    g = torch.Generator().manual_seed(115)
+    mine = dvcp.feat_embedding_layer().eval().to(cuda)
+    B, M, Q = 1, 40, 9
+    xyz = (torch.rand(B, 3, M, generator=g) * 2 - 1).to(cuda)
+    half = torch.randn(B, M, 32, generator=g).half().to(cuda)
+    wide = half.float()
+    qry = (torch.rand(B, Q, 3, generator=g) * 2 - 1).to(cuda)
+    dist, idx, _ = ops.knn(xyz, qry, 32, ref_pdim=2, qry_pdim=1)
+    got, want = (torch.full((B, Q, 32), float("nan"), device=cuda) for _ in range(2))
+    for name, table, out in (("dvcp_dfe_tgt_f16", half, got), ("dvcp_dfe_tgt", wide, want)):
+        _lib.call(name, _lib.F32, ptr(xyz), xyz.stride(0), xyz.stride(1), xyz.stride(2), M, ptr(table), ptr(qry),
+                  ptr(dist), ptr(idx), B, Q, ptr(mine.packed_params()), ptr(out), stream())
+    assert torch.isfinite(want).all() and torch.equal(got, want)
+    assert torch.equal(want, ops.dfe_tgt(xyz, wide, qry, dist, idx, mine.packed_params(), ref_pdim=2))
+
+
 
 def test_fe_chain_with_fps_pair_equals_serial(cuda, monkeypatch):
     """The feature extractor with the opt-in paired layer-2/3 FPS (DVCP_FPS_PAIR=1) against the

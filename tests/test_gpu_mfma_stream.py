@@ -1,4 +1,4 @@
-"""The split-3 MFMA kernels (csrc/sa_mfma_*.hip, csrc/dfe_mfma.hip, csrc/cpg.hip; the split
+"""The split-3 MFMA kernels (csrc/sa_mfma_*.hip, csrc/dfe_tgt.hip, csrc/cpg.hip; the split
 itself in csrc/split3.h) may change their instruction stream -- how the split is written, what the
 compiler may pack, where the VALU work sits between the MFMAs -- but never their arithmetic: the
 same pieces, the same six products in the same order.  So

@@ -3,7 +3,7 @@
 # objects of every other source, into dvcp/libdvcp_hip_<name>.so (loaded by tools/gpu_ab_*.sh
 # through DVCP_LIB_PATH; the in-tree library is not touched).  Delete the variants before a round
 # ends (they travel with every gpurun call).
-#   tools/build_variant.sh <name> <source stem, e.g. dfe_mfma> [-DNAME=VALUE ...]
+#   tools/build_variant.sh <name> <source stem, e.g. dfe_tgt> [-DNAME=VALUE ...]
 set -e
 name=$1; stem=$2; shift 2
 cd "$(dirname "$0")/../deepvcp-pointcloud-registration_amd"

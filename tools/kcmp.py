@@ -8,7 +8,9 @@ one) or an offload bundle, which is unbundled for gfx950 first.  The kernels of 
 together are compared with OLD's: every kernel (a function with a `.kd` descriptor) is
 disassembled with llvm-objdump -d and its whole text -- mnemonics, operands and encodings, the
 address column dropped -- must match.  A kernel's own symbol in the comments of its branches
-(`<symbol+0x...>`) is dropped too, so a renamed kernel still compares.  --rename (repeatable)
+(`<symbol+0x...>`) is dropped too, so a renamed kernel still compares, and so is the `s_nop 0`
+padding behind a kernel's last instruction (it fills the gap to the next symbol or to the section's
+end, so it depends on which kernel follows in the object, not on the kernel).  --rename (repeatable)
 replaces OLD_PREFIX at the start of OLD's demangled kernel names by NEW_PREFIX before the names are
 matched, for kernels that were renamed or whose template list changed.  Prints the identical, differing, missing (only in OLD) and
 added (only in NEW) kernels, a kernel found in two NEW objects, and exits 1 unless every kernel of
@@ -55,6 +57,9 @@ def kernels(path, tmp):
             # "\tinsn operands  // 000000001234: ENCODING ..." -> drop the address
             ln = re.sub(r"//\s*[0-9A-Fa-f]+:", "//", ln).strip()
             funcs[name].append(ln.replace(f"<{name}+", "<+"))  # branch targets: offset only
+    for text in funcs.values():  # s_nop padding behind the last instruction, up to the next symbol or the
+        while text and text[-1].split("//")[0].strip() == "s_nop 0":  # section's end: not part of the function
+            text.pop()
     names = sorted(kds)
     filt = shutil.which("llvm-cxxfilt", path=LLVM) or shutil.which("llvm-cxxfilt") or shutil.which("c++filt")
     pretty = run(filt, *names).splitlines() if names and filt else names
